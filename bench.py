@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: batched ICP scan-pairs/s (1081-point scans) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
 Workload (BASELINE.json configs[2], "Batched ICP: 10k synthetic scan-pairs x
@@ -17,12 +17,23 @@ for N > 1, the RCCL all-gather of the resulting SE(2) edges (the exchange step
 of the north star).  Total work is fixed as N grows ("scaling": "strong");
 ``--weak`` gives every rank its own P-pair stream (seed 2025 + rank) instead.
 
-Printed: ONE JSON line (rank 0) with the driver's contract fields plus
-``roofline`` (dominant kernel: the FP32 VALU roofline over the candidate
-distances it actually evaluates, the VALU issue fraction from the committed
-PMC profile, the HBM rate beside it),
-``cpu_baseline`` (NumPy port of the reference, timed on this host) and
-secondary pose-graph numbers (``pgo``).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line
+(rank 0) with the driver's contract fields (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` = wall milliseconds of one
+timed step) and the workload's ``config``.  ``--dump-outputs DIR`` also writes
+what the last timed step computed, as the caller of ``IcpBatch.result()``
+receives it, to ``DIR/tf.npy`` (B, 3, 3), ``DIR/err.npy`` (B,) and
+``DIR/iters.npy`` (B,), all float64 (N > 1: rank 0's shard, plus the
+all-gathered edges of every rank as ``DIR/gathered.npy``).  The workload is
+seeded, so the same arguments give the same inputs in every run.
+
+``--full`` adds, after the timed steps and outside them, ``roofline``
+(dominant kernel: the FP32 VALU roofline over the candidate distances it
+actually evaluates, counted by one more launch, the VALU issue fraction from
+the committed PMC profile, the HBM rate beside it), ``cpu_baseline`` (NumPy
+port of the reference, timed on this host), ``parity`` of the timed results
+against that port, the secondary pose-graph numbers (``pgo``) and the single
+drop-in call (``c1``).
 """
 import argparse
 import json
@@ -43,6 +54,7 @@ FLOP_PER_EVAL = 5                 # 2 sub, 2 mul, 1 add per candidate distance
 # instructions per candidate): 256 CU x 2.4 GHz x 64 lanes / 8
 ISSUE_BOUND_EVALS_PER_S = 4.9e12
 DEFAULT_SHARD = "balanced"
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000   # --dump-outputs writes less than 64 MB in all
 KERNEL_SOURCES = ("icp-slam-with-loop-closure_amd/csrc/icp_kernels.hip", "icp-slam-with-loop-closure_amd/csrc/common.hpp")
 
 
@@ -70,8 +82,12 @@ def parse():
     p.add_argument("--beams", type=int, default=1081)
     p.add_argument("--weak", action="store_true",
                    help="every rank runs its own P-pair stream (weak scaling) instead of a shard of one")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-pgo", action="store_true")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's results to DIR/<name>.npy (float64)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also report roofline, cpu_baseline, parity, pgo and c1")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    p.add_argument("--no-pgo", action="store_true", help="with --full: leave pgo and c1 out")
     p.add_argument("--cpu-sample", type=int, default=192, help="pairs in the CPU baseline sample")
     p.add_argument("--cpu-workers", type=int, default=0, help="0 = every core this job may use")
     p.add_argument("--instance", type=int, default=-1, help="force a kernel instance (diagnostics)")
@@ -90,7 +106,28 @@ def parse():
     p.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL on ROCm); gloo only for dry runs")
     p.add_argument("--shard", default=DEFAULT_SHARD, choices=("contiguous", "balanced"),
                    help="strong-scaling split of the pairs over the ranks (slamhip.dist)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, res, gathered=None):
+    """The arrays a caller of the timed path receives, as float64 ``.npy``
+    files (10,000 pairs: under 1 MB in all).  An array above its share of
+    DUMP_LIMIT_BYTES is cut to a fixed, seeded sample of its rows (in order)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"tf": res.tf, "err": res.err, "iters": res.iters}
+    if gathered is not None:
+        g = gathered.cpu().numpy()
+        arrays["gathered"] = g.reshape(-1, g.shape[-1])
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        rows = share // max(a[:1].nbytes, 1)
+        if len(a) > rows:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), size=rows, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def init_dist(args):
@@ -486,6 +523,88 @@ def main():
 
     ms_per_step = dt_max / args.steps * 1e3
     value = pairs_all * args.steps / dt_max
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, gathered)
+    sel = lib.slam_icp_selected_instance(int(n1.max()))
+    import ctypes
+    bb, qq = ctypes.c_int32(), ctypes.c_int32()
+    lib.slam_icp_instance_shape(sel, ctypes.byref(bb), ctypes.byref(qq))
+    out = {
+        "metric": "ICP scan-pairs/sec (1081-pt scans)",
+        "value": round(value, 2),
+        "unit": "scan-pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (SURVEY.md §8(d) ray-cast room, 1081 beams/270 deg, 0.01 m noise; EECS_3 unavailable offline)",
+        "exchange_timeouts": timeouts,
+        "config": {"workload": "C3 batched ICP: consecutive scan pairs of a synthetic stream, "
+                               "scripts/main.py params (eps 0.05, max_iters 100)",
+                   "pairs_per_rank": B, "pairs_total": int(pairs_all), "points_per_scan": int(n1.max()),
+                   "mean_icp_iterations": round(iters_all / pairs_all, 3),
+                   "kernel_instance": f"{bb.value}x{qq.value}", "parallelism": f"dp{world}",
+                   "sharding": "weak (own stream per rank)" if args.weak else args.shard,
+                   "tier_profile": tier_profile(B)},
+    }
+    if per_rank is not None:
+        out["per_rank"] = {"kernel_ms": [round(r[0], 4) for r in per_rank],
+                           "pairs": [int(r[1]) for r in per_rank],
+                           "wall_ms_per_step": [round(r[2], 4) for r in per_rank],
+                           "max_shard_pairs": int(max(r[1] for r in per_rank)),
+                           "slowest_rank": int(np.argmax([r[0] for r in per_rank])),
+                           "exchange_timeouts": [int(r[3]) for r in per_rank],
+                           "all_gather_unpermuted_ok_rank0": gather_ok,
+                           "longest_pair_iterations": [int(r[4]) for r in per_rank],
+                           "shard": args.shard if not args.weak else "weak",
+                           "note": "kernel_ms: HIP events around batch.launch() on each rank's stream; "
+                                   "wall: the rank's timed loop incl. the all-gather; exchange_timeouts: "
+                                   "slam_icp_gang_timeouts() over the timed steps (repaired bit-identically)"}
+    if args.full:
+        out["roofline"] = roofline_block(torch, lib, batch, ss, B, kern_ms, evals)
+        full_extras(out, args, world, scans, src, dst, inits, res, B)
+    print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_extras(out, args, world, scans, src, dst, inits, res, B):
+    """--full: the CPU baseline, parity of the timed results against the CPU
+    port, and the secondary workloads, added to the result line ``out``."""
+    if world == 1 and not args.no_cpu_baseline:
+        try:
+            workers = args.cpu_workers or default_cpu_workers()
+            out["cpu_baseline"], ref = cpu_baseline(scans, src, dst, inits, args.cpu_sample, workers)
+            out["parity"] = parity_block(res, ref)
+        except Exception as e:   # keep the GPU line even if the host pool fails
+            out["cpu_baseline"] = {"error": repr(e)}
+    if "parity" not in out:
+        # no CPU baseline run (N > 1 or --no-cpu-baseline): a small vectorised sample
+        idx = np.linspace(0, B - 1, min(B, 6)).astype(int) if B else []
+        ref = {int(i): _oracle_pair(np.c_[scans[src[i]], np.ones(len(scans[src[i]]))],
+                                    np.c_[scans[dst[i]], np.ones(len(scans[dst[i]]))], inits[i].copy(), False)
+               for i in idx}
+        if ref:
+            out["parity"] = parity_block(res, ref)
+            out["parity"]["scope"] = "rank 0's shard"
+    if world == 1 and not args.no_pgo:
+        try:
+            out["pgo"] = pgo_bench()
+        except Exception as e:
+            out["pgo"] = {"error": repr(e)}
+        try:
+            out["c1"] = c1_bench()
+        except Exception as e:
+            out["c1"] = {"error": repr(e)}
+
+
+def roofline_block(torch, lib, batch, ss, B, kern_ms, evals):
+    """--full: the dominant kernel's rates over the timed steps' ``kern_ms``
+    (HIP events around each timed launch) beside its bounds."""
     # dominant kernel: slam_icp_batch_f64 on rank 0 (its own pairs).  Work is
     # counted as the candidate distances the kernel actually evaluates (exact
     # pruning skips most of the n1*n2 brute-force set): one counting launch,
@@ -529,107 +648,41 @@ def main():
                 traffic = valu_issue = valu_per_eval = None
         except Exception:
             traffic = None
-    sel = lib.slam_icp_selected_instance(int(n1.max()))
-    import ctypes
-    bb, qq = ctypes.c_int32(), ctypes.c_int32()
-    lib.slam_icp_instance_shape(sel, ctypes.byref(bb), ctypes.byref(qq))
-    out = {
-        "metric": "ICP scan-pairs/sec (1081-pt scans)",
-        "value": round(value, 2),
-        "unit": "scan-pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak" if args.weak else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (SURVEY.md §8(d) ray-cast room, 1081 beams/270 deg, 0.01 m noise; EECS_3 unavailable offline)",
-        "exchange_timeouts": timeouts,
-        "config": {"workload": "C3 batched ICP: consecutive scan pairs of a synthetic stream, "
-                               "scripts/main.py params (eps 0.05, max_iters 100)",
-                   "pairs_per_rank": B, "pairs_total": int(pairs_all), "points_per_scan": int(n1.max()),
-                   "mean_icp_iterations": round(iters_all / pairs_all, 3),
-                   "kernel_instance": f"{bb.value}x{qq.value}", "parallelism": f"dp{world}",
-                   "sharding": "weak (own stream per rank)" if args.weak else args.shard,
-                   "tier_profile": tier_profile(B)},
-        "roofline": {
-            # achieved = candidate evaluations per second against
-            # the VALU issue bound 4.9e12 /s (= 24.5 TFLOP/s at 5 flops each)
-            "bound": "valu",
-            "kernel": "slam_icp_batch_f64 (icp_kernel, %s)" % (
-                {2: "fp32 screen with exact pruning + fp64 certification",
-                 1: "fp32 screen + fp64 certification", 0: "exact fp64 scan"}[mode]),
-            "achieved": round(flops, 3),
-            "peak": round(FLOP_PER_EVAL * ISSUE_BOUND_EVALS_PER_S / 1e12, 3),
-            "unit": "TFLOP/s",
-            "frac": round(evals_per_s / ISSUE_BOUND_EVALS_PER_S, 4),
-            "traffic": traffic,
-            "kernel_ms": round(kern_ms, 4),
-            "candidate_evals_per_s": round(evals_per_s, 1),
-            "issue_bound_evals_per_s": ISSUE_BOUND_EVALS_PER_S,
-            "candidate_evals_frac_of_issue_bound": round(evals_per_s / ISSUE_BOUND_EVALS_PER_S, 4),
-            "fp64_flop_frac": round(flops / FP64_VALU_PEAK_TFLOPS, 4),
-            "fp32_flop_frac": round(flops / FP32_VALU_PEAK_TFLOPS, 4),
-            "fp64_peak_tflops": FP64_VALU_PEAK_TFLOPS,
-            "fp32_peak_tflops": FP32_VALU_PEAK_TFLOPS,
-            "candidate_evals_performed_per_launch": performed,
-            "brute_force_evals_per_launch": evals,
-            "pruning_factor": round(evals / max(performed, 1.0), 2),
-            "brute_force_equivalent_evals_per_s": round(evals / (kern_ms * 1e-3), 1),
-            "valu_busy_frac": valu_issue,
-            "valu_busy_source": "profiles/pmc_traffic.json (rocprofv3 SQ_ACTIVE_INST_VALU / GRBM_GUI_ACTIVE, C3 batch)",
-            "pmc_profile": pmc_src,
-            "valu_lane_insts_per_candidate_eval": (round(valu_per_eval * B / performed, 2)
-                                                   if valu_per_eval and performed else None),
-            "brute_force_equivalent_note": "pruning skips candidates exactly; the brute-force-equivalent rate is "
-                                           "not a roofline figure",
-            "hbm": {"achieved": round(hbm_gbps, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(hbm_gbps / HBM_PEAK_GBPS, 6), "algorithmic_bytes_per_launch": alg_bytes},
-        },
+    return {
+        # achieved = candidate evaluations per second against
+        # the VALU issue bound 4.9e12 /s (= 24.5 TFLOP/s at 5 flops each)
+        "bound": "valu",
+        "kernel": "slam_icp_batch_f64 (icp_kernel, %s)" % (
+            {2: "fp32 screen with exact pruning + fp64 certification",
+             1: "fp32 screen + fp64 certification", 0: "exact fp64 scan"}[mode]),
+        "achieved": round(flops, 3),
+        "peak": round(FLOP_PER_EVAL * ISSUE_BOUND_EVALS_PER_S / 1e12, 3),
+        "unit": "TFLOP/s",
+        "frac": round(evals_per_s / ISSUE_BOUND_EVALS_PER_S, 4),
+        "traffic": traffic,
+        "kernel_ms": round(kern_ms, 4),
+        "candidate_evals_per_s": round(evals_per_s, 1),
+        "issue_bound_evals_per_s": ISSUE_BOUND_EVALS_PER_S,
+        "candidate_evals_frac_of_issue_bound": round(evals_per_s / ISSUE_BOUND_EVALS_PER_S, 4),
+        "fp64_flop_frac": round(flops / FP64_VALU_PEAK_TFLOPS, 4),
+        "fp32_flop_frac": round(flops / FP32_VALU_PEAK_TFLOPS, 4),
+        "fp64_peak_tflops": FP64_VALU_PEAK_TFLOPS,
+        "fp32_peak_tflops": FP32_VALU_PEAK_TFLOPS,
+        "candidate_evals_performed_per_launch": performed,
+        "brute_force_evals_per_launch": evals,
+        "pruning_factor": round(evals / max(performed, 1.0), 2),
+        "brute_force_equivalent_evals_per_s": round(evals / (kern_ms * 1e-3), 1),
+        "valu_busy_frac": valu_issue,
+        "valu_busy_source": "profiles/pmc_traffic.json (rocprofv3 SQ_ACTIVE_INST_VALU / GRBM_GUI_ACTIVE, C3 batch)",
+        "pmc_profile": pmc_src,
+        "valu_lane_insts_per_candidate_eval": (round(valu_per_eval * B / performed, 2)
+                                               if valu_per_eval and performed else None),
+        "brute_force_equivalent_note": "pruning skips candidates exactly; the brute-force-equivalent rate is "
+                                       "not a roofline figure",
+        "hbm": {"achieved": round(hbm_gbps, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": round(hbm_gbps / HBM_PEAK_GBPS, 6), "algorithmic_bytes_per_launch": alg_bytes},
     }
-    if per_rank is not None:
-        out["per_rank"] = {"kernel_ms": [round(r[0], 4) for r in per_rank],
-                           "pairs": [int(r[1]) for r in per_rank],
-                           "wall_ms_per_step": [round(r[2], 4) for r in per_rank],
-                           "max_shard_pairs": int(max(r[1] for r in per_rank)),
-                           "slowest_rank": int(np.argmax([r[0] for r in per_rank])),
-                           "exchange_timeouts": [int(r[3]) for r in per_rank],
-                           "all_gather_unpermuted_ok_rank0": gather_ok,
-                           "longest_pair_iterations": [int(r[4]) for r in per_rank],
-                           "shard": args.shard if not args.weak else "weak",
-                           "note": "kernel_ms: HIP events around batch.launch() on each rank's stream; "
-                                   "wall: the rank's timed loop incl. the all-gather; exchange_timeouts: "
-                                   "slam_icp_gang_timeouts() over the timed steps (repaired bit-identically)"}
-    if world == 1 and not args.no_cpu_baseline:
-        try:
-            workers = args.cpu_workers or default_cpu_workers()
-            out["cpu_baseline"], ref = cpu_baseline(scans, src, dst, inits, args.cpu_sample, workers)
-            out["parity"] = parity_block(res, ref)
-        except Exception as e:   # keep the GPU line even if the host pool fails
-            out["cpu_baseline"] = {"error": repr(e)}
-    if "parity" not in out:
-        # no CPU baseline run (N > 1 or --no-cpu-baseline): a small vectorised sample
-        idx = np.linspace(0, B - 1, min(B, 6)).astype(int) if B else []
-        ref = {int(i): _oracle_pair(np.c_[scans[src[i]], np.ones(len(scans[src[i]]))],
-                                    np.c_[scans[dst[i]], np.ones(len(scans[dst[i]]))], inits[i].copy(), False)
-               for i in idx}
-        if ref:
-            out["parity"] = parity_block(res, ref)
-            out["parity"]["scope"] = "rank 0's shard"
-    if world == 1 and not args.no_pgo:
-        try:
-            out["pgo"] = pgo_bench()
-        except Exception as e:
-            out["pgo"] = {"error": repr(e)}
-        try:
-            out["c1"] = c1_bench()
-        except Exception as e:
-            out["c1"] = {"error": repr(e)}
-    print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+
 
 
 if __name__ == "__main__":

@@ -30,7 +30,7 @@ def test_bench_two_ranks_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--pairs", "400", "--steps", "2", "--warmup", "1",
-           "--dist-backend", "gloo", "--no-pgo"]
+           "--dist-backend", "gloo", "--full", "--no-pgo"]
     p = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=100)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -5,7 +5,7 @@ for r in 1 2; do
 for v in cur "$@"; do
   if [ "$v" = cur ]; then unset SLAMHIP_LIB; else export SLAMHIP_LIB=ab/$v/libslamhip.so; fi
   for n in 5000 2500 1250; do
-    res=$(timeout -k 10 120 python bench.py --no-cpu-baseline --no-pgo --steps 10 --pairs $n 2>/dev/null) || { echo "$v $n FAILED"; exit 1; }
+    res=$(timeout -k 10 120 python bench.py --full --no-cpu-baseline --no-pgo --steps 10 --pairs $n 2>/dev/null) || { echo "$v $n FAILED"; exit 1; }
     echo "$v pairs $n $(echo "$res" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["roofline"]["kernel_ms"], d["parity"]["ok"])')"
   done
 done

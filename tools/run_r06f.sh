@@ -6,4 +6,4 @@ for env in "SHARD_SEED=2025" "SHARD_SEED=7" "SHARD_SEED=2025 SHARD_DROPOUT=0.35"
   env $env timeout -k 10 300 python -u tools/shard_sweep.py auto >> gpurun_out/r06_profile_validation2.txt 2>&1
 done
 SHARD_WIDE_GROUPS=2 SHARD_N=2 SHARD_MODE=balanced timeout -k 10 300 python -u tools/shard_sweep.py 64,24,4,0,1,-1,1,8193,-1,96,30,3,16,2 64,24,4,0,1,-1,1,8193,-1,96,30,3,24,2 64,24,4,0,1,-1,1,8193,-1,96,30,3,32,2 > gpurun_out/r06_mix_sweep3.txt 2>&1
-timeout -k 10 400 python -u bench.py > gpurun_out/r06_bench_a.json 2> gpurun_out/r06_bench_a.err
+timeout -k 10 400 python -u bench.py --full > "${OUT:-.}/r06_bench_a.json" 2> "${OUT:-.}/r06_bench_a.err"
