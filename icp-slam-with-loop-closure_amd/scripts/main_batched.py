@@ -15,7 +15,11 @@ grids of src/visualization.py:74-98 (``<name>_og.png``, ``<name>.map`` with
 Inputs: ``dataset`` is an ``.npz`` scan stream (slamhip.dataset.save) or a
 generator spec ``synthetic:<walk|loop>:<n_scans>[:<seed>]``; for ``loop``
 datasets ``--manual-loop-closures auto`` uses the generator's ground-truth
-loop pairs.  Out of scope here (flags accepted, ignored): image-based loop
+loop pairs.  ``--loop-closure-init csm`` (new, opt-in) starts every
+loop-closure ICP from the batched correlative scan match of its pair
+(slamhip.csm) instead of the reference's identity; ``--csm-window-m``,
+``--csm-angle-window-deg`` and ``--csm-angle-step-deg`` size its search.
+Out of scope here (flags accepted, ignored): image-based loop
 closure detection (OpenCV) and the matplotlib figures.
 
     python icp-slam-with-loop-closure_amd/scripts/main_batched.py synthetic:loop:2000:3 \\
@@ -52,6 +56,12 @@ def parse(argv=None):
                    help="text file of (i, j) rows, or 'auto' for a synthetic loop dataset's ground truth")
     p.add_argument("--loop-closure-icp-error", default=30, type=float,
                    help="accepted for compatibility; the manual path uses the reference's fixed 30")
+    p.add_argument("--loop-closure-init", default="identity", choices=["identity", "csm"],
+                   help="identity = the reference's ICP start (default); csm = correlative scan match of every pair")
+    p.add_argument("--csm-window-m", default=1.5, type=float,
+                   help="csm: half-width of the shift search (m), in cells of 0.05 m")
+    p.add_argument("--csm-angle-window-deg", default=180.0, type=float, help="csm: half-width of the angle search")
+    p.add_argument("--csm-angle-step-deg", default=1.5, type=float, help="csm: angle bin spacing")
     p.add_argument("--icp-recompute", action="store_true")
     p.add_argument("--optimizer", default="sgd", choices=["sgd", "gn"],
                    help="sgd = the reference's relaxation (default); gn = Gauss-Newton")
@@ -75,7 +85,19 @@ def parse(argv=None):
         p.error("--program-end precedes --program-start")
     if a.program_start != "scan_matching" and not a.pose_graph:
         p.error("starting after scan matching needs --pose-graph")
+    if not (a.csm_window_m >= 0 and 0 < a.csm_angle_step_deg and 0 <= a.csm_angle_window_deg <= 180):
+        p.error("--csm-window-m >= 0, --csm-angle-step-deg > 0 and 0 <= --csm-angle-window-deg <= 180 expected")
     return a
+
+
+def csm_params(a):
+    """CsmParams of the --csm-* flags: a (2 w + 1)^2 window of 0.05 m cells, angle
+    bins of the given step over +-window (the defaults give CsmParams())."""
+    from slamhip.csm import CsmParams
+    res = CsmParams().res
+    side = 2 * int(round(a.csm_window_m / res)) + 1
+    n_theta = max(1, int(round(2 * a.csm_angle_window_deg / a.csm_angle_step_deg)))
+    return CsmParams(res=res, n_theta=n_theta, d_theta=2 * np.pi / (360.0 / a.csm_angle_step_deg), nx=side, ny=side)
 
 
 def save_map(a, poses, scans, name, report):
@@ -146,9 +168,10 @@ def run(a):
             else:
                 matches = pipeline.read_manual_loop_closures(a.manual_loop_closures)
             t0 = time.perf_counter()
-            ok = pipeline.manual_loop_closures(pg, scans, matches)
+            ok = pipeline.manual_loop_closures(pg, scans, matches, init=a.loop_closure_init,
+                                               csm=csm_params(a) if a.loop_closure_init == "csm" else None)
             report["loop_closures"] = {"annotated": int(len(matches)), "accepted": int(ok.sum()),
-                                       "s": round(time.perf_counter() - t0, 3)}
+                                       "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
         pg.save(out("loop_closure_pose_graph.pickle"))
         pg.export_g2o(out("loop_closure_pose_graph.g2o"))
     if a.program_end == "loop_closure":

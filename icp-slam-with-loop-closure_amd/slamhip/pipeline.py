@@ -65,19 +65,43 @@ def read_manual_loop_closures(fname):
     return np.atleast_2d(m).reshape(-1, 2)
 
 
+LOOP_CLOSURE_INITS = ("identity", "csm")
+
+
+def check_loop_closure_init(init):
+    if init not in LOOP_CLOSURE_INITS:
+        raise ValueError(f"unknown loop-closure init {init!r} ({' | '.join(LOOP_CLOSURE_INITS)})")
+
+
+def loop_closure_inits(scanset, src, dst, init="identity", csm=None):
+    """(B, 3, 3) initial transforms of the loop-closure ICP launch
+    icp(pc1 = src[b], pc2 = dst[b]): ``"identity"`` (the reference's
+    ``np.eye(3)``, the default) or ``"csm"`` — the batched correlative scan
+    match of the same pairs (``slamhip.csm.csm_batch``; ``csm``: its
+    ``CsmParams``, None for the defaults), for loops closed at another heading."""
+    check_loop_closure_init(init)
+    if init == "identity":
+        return np.broadcast_to(np.eye(3), (len(src), 3, 3))
+    from . import csm as _csm
+    return _csm.csm_batch(scanset, src, dst, params=csm if csm is not None else _csm.CsmParams()).tf
+
+
 def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
-                         err_thresh=LOOP_CLOSURE_ICP_ERROR, scanset=None):
+                         err_thresh=LOOP_CLOSURE_ICP_ERROR, scanset=None, init="identity", csm=None):
     """Stage 2, manual path (``scripts/main.py:298-307``): ICP(pc_i, pc_j,
     init = I) for every annotated pair in ONE launch; constraints are added
     in file order (``add_constraint`` overwrites a repeated (i, j) in place,
     networkx semantics), exactly as the reference's serial loop does.
+    ``init="csm"`` (new, opt-in) starts every ICP from the correlative scan
+    match of its pair instead of the identity (``loop_closure_inits``).
     Returns the boolean mask of accepted matches."""
     from . import icp as _icp
+    check_loop_closure_init(init)
     matches = np.asarray(matches, dtype=np.int64).reshape(-1, 2)
     if len(matches) == 0:
         return np.zeros(0, dtype=bool)
     ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
-    inits = np.broadcast_to(np.eye(3), (len(matches), 3, 3))
+    inits = loop_closure_inits(ss, matches[:, 0], matches[:, 1], init, csm)
     batch = _icp.IcpBatch(ss, matches[:, 0], matches[:, 1], inits, epsilon=epsilon, max_iters=max_iters)
     batch.launch()
     r = batch.result()

@@ -19,12 +19,18 @@ so the module (and ``scripts/main.py``) imports on a host without cv2.
   descriptor matching stay OpenCV's (ImportError without it); the ICP
   alignment of the accepted image matches (reference :136-142, a joblib
   fan-out) is one batched launch.
+
+New, opt-in (a trailing keyword of both functions; the reference's call shapes
+bind unchanged): ``init="csm"`` starts every ICP from the batched correlative
+scan match of its pair (``slamhip.csm``; ``csm``: its ``CsmParams``) instead
+of the identity, for loops closed at another heading.  The default
+``init="identity"`` is the reference's behaviour.
 """
 import numpy as np
 import scipy.spatial
 
 from slamhip import icp as _k
-from slamhip.pipeline import add_loop_constraint
+from slamhip.pipeline import add_loop_constraint, check_loop_closure_init, loop_closure_inits
 
 
 def _cv2():
@@ -39,6 +45,16 @@ def _cv2():
 def _homog(p):
     p = np.asarray(p, dtype=np.float64)
     return np.c_[p[:, :2], np.ones(len(p))]
+
+
+def _icp_pairs(pc1_list, pc2_list, init, csm):
+    """``slamhip.icp.icp_pairs`` (eps 0.05, max_iters 100) over one ScanSet
+    that the opt-in correlative scan match of the same pairs shares."""
+    scans = [s for pair in zip(pc1_list, pc2_list) for s in pair]
+    B = len(pc1_list)
+    src, dst = np.arange(0, 2 * B, 2), np.arange(1, 2 * B, 2)
+    ss = _k.ScanSet(scans)
+    return _k.icp_batch(ss, src, dst, loop_closure_inits(ss, src, dst, init, csm), epsilon=0.05, max_iters=100)
 
 
 def _path_geometry(poses):
@@ -62,13 +78,15 @@ def proximity_candidates(poses, min_dist_along_path=2, max_dist=1):
     return out
 
 
-def detect_proximity(pose_graph, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110):
+def detect_proximity(pose_graph, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110,
+                     init="identity", csm=None):
+    check_loop_closure_init(init)
     cand = proximity_candidates(pose_graph.poses, min_dist_along_path, max_dist)
     if not cand:
         return
     # icp(pc_j, pc_i) for every candidate, one launch (reference :33-35)
-    res = _k.icp_pairs([_homog(lidar_points[j]) for _, j in cand], [_homog(lidar_points[i]) for i, _ in cand],
-                       np.stack([np.eye(3)] * len(cand)), epsilon=0.05, max_iters=100)
+    res = _icp_pairs([_homog(lidar_points[j]) for _, j in cand], [_homog(lidar_points[i]) for i, _ in cand],
+                     init, csm)
     used = set()
     for b, (i, j) in enumerate(cand):
         if i in used or j in used:
@@ -122,7 +140,9 @@ def matchify(desc1, desc2, i, j, n_matches, approximate_match):
 
 def detect_images_direct_similarity(pose_graph, lidar_points, images, image_rate=1, min_dist_along_path=5,
                                     image_err_thresh=125, n_matches=10, icp_err_thresh=30, save_dists=False,
-                                    save_matches=False, n_jobs=-1, approximate_match=True):
+                                    save_matches=False, n_jobs=-1, approximate_match=True,
+                                    init="identity", csm=None):
+    check_loop_closure_init(init)
     cv2 = _cv2()
     from joblib import Parallel, delayed
     d, walked = _path_geometry(pose_graph.poses)
@@ -160,9 +180,8 @@ def detect_images_direct_similarity(pose_graph, lidar_points, images, image_rate
     if not good:
         return
     # reference :136-142: icp(pc_i, pc_j, init eye, max_iters 100, eps 0.05) per match -> one launch
-    res = _k.icp_pairs([_homog(lidar_points[i * image_rate]) for i, _ in good],
-                       [_homog(lidar_points[j * image_rate]) for _, j in good],
-                       np.stack([np.eye(3)] * len(good)), epsilon=0.05, max_iters=100)
+    res = _icp_pairs([_homog(lidar_points[i * image_rate]) for i, _ in good],
+                     [_homog(lidar_points[j * image_rate]) for _, j in good], init, csm)
     for b, (i0, j0) in enumerate(good):
         i, j = i0 * image_rate, j0 * image_rate
         if float(res.err[b]) < icp_err_thresh:

@@ -252,6 +252,48 @@ int slam_grid_update_i8(const double* gpts, const int64_t* scan_off, int32_t S, 
                         double min_x, double min_y, double cell_width, int32_t H, int32_t W, int32_t k_hit,
                         int32_t k_miss, int8_t* grid, void* work, void* stream);
 
+/* ---- correlative scan matcher (csrc/csm_kernels.hip) -----------------------
+ * A brute-force, single-resolution correlative scan match (Olson 2009) of B
+ * scan pairs: an initial guess for loop-closure ICP that does not need the two
+ * scans to share a heading.  The reference has no counterpart (it starts every
+ * loop-closure ICP from identity); new since ABI 101.
+ *   pts, scan_off, src_scan (query q), dst_scan (reference r): as
+ *             slam_icp_batch_f64; the match follows icp(pc1 = q, pc2 = r),
+ *             a transform T with T q ~ r
+ *   centre    float64[B][3]  search centre (theta0, tx0, ty0) of pair b
+ *   rot       float64[B][n_theta][2]  (cos, sin) of theta_k = theta0 +
+ *             (k - n_theta / 2) d_theta, evaluated by the caller (np.cos /
+ *             np.sin of the Python float, like pose4 above)
+ *   res, G    cell width and cells per side (even) of the look-up table; its
+ *             origin is -(G / 2) res on both axes
+ *   nx, ny    shift window in cells (any parity)
+ * Table L (G x G, row = y): 2 on every cell floor((p - origin) / res) that
+ * holds a reference point, 1 on the 8 neighbours of such a cell that hold
+ * none, 0 elsewhere (each of the 9 cells clipped on its own).  Query cells per
+ * angle: X = (c x - s y) + tx0, Y = (s x + c y) + ty0, ix = floor((X - origin)
+ * / res), iy likewise (true fp64 division, no contraction).  Score
+ * S[k][j][i] = sum over query points of L[iy + j - ny / 2][ix + i - nx / 2],
+ * a cell outside the grid (or beyond int32) adding 0.  Only integers are
+ * summed: the result does not depend on summation order or launch shape.
+ *   out_best    int32[B][4]  maximum score, then k, j, i of the maximum with
+ *               the smallest flat index (k ny + j) nx + i
+ *   out_scores  int32[B][n_theta][ny][nx] the whole volume, or NULL
+ *   work        slam_csm_work_size(B, G, n_theta, ny, nx) BYTES
+ * The caller assembles T from (c_k, s_k) and tx0 + (i - nx / 2) res, ty0 +
+ * (j - ny / 2) res.  SLAM_EINVAL for a null array, B <= 0, an odd or
+ * non-positive G, a non-positive res, n_theta, nx or ny, or a score volume
+ * n_theta ny nx of 2^31 or more entries (slam_csm_work_size returns
+ * SLAM_EINVAL for such a shape too). */
+int64_t slam_csm_work_size(int32_t B, int32_t G, int32_t n_theta, int32_t ny, int32_t nx);
+int slam_csm_batch(const double* pts, const int64_t* scan_off, const int32_t* src_scan, const int32_t* dst_scan,
+                   const double* centre, const double* rot, int32_t B, double res, int32_t G, int32_t n_theta,
+                   int32_t nx, int32_t ny, int32_t* out_best, int32_t* out_scores, void* work, void* stream);
+/* Diagnostics: the score kernel gathers the table one byte per lane (1) or as
+ * unaligned dwords, 4 adjacent shifts per lane summed as packed 16-bit pairs
+ * (4, default; DESIGN.md section 3.5 has the A/B).  Per host thread; identical
+ * results. */
+int slam_csm_set_gather(int width);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
