@@ -996,14 +996,23 @@ int64_t bcr_work_size(int32_t nv, int32_t W, int32_t mc) {
 // bcr_load_kernel; *dx_out is then the nv x mc solution block (row stride mc).
 // default: the explicit-inverse levels (gn_bcr_gj.hip); the Cholesky paths
 // below stay selectable for A/B (SLAMHIP_BCR_CHOL=1, SLAMHIP_BCR_LEGACY=1)
-bool bcr_gj_default() {
-    static const bool chol = [] {
-        const char* e = getenv("SLAMHIP_BCR_CHOL");
-        const char* l = getenv("SLAMHIP_BCR_LEGACY");
-        return (e && e[0] == '1') || (l && l[0] == '1');
-    }();
-    return !chol;
+static bool env_is_one(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '1';
 }
+bool bcr_env_chol() {
+    static const bool on = env_is_one("SLAMHIP_BCR_CHOL");
+    return on;
+}
+bool bcr_env_legacy() {
+    static const bool on = env_is_one("SLAMHIP_BCR_LEGACY");
+    return on;
+}
+bool bcr_env_odd_mfma() {
+    static const bool on = env_is_one("SLAMHIP_BCR_ODD_MFMA");
+    return on;
+}
+bool bcr_gj_default() { return !(bcr_env_chol() || bcr_env_legacy()); }
 
 // preloaded: the caller's assembly already wrote the explicit-inverse path's
 // D, E0 and bz (gn_assemble_kernel with a block layout): no load launch.
@@ -1070,10 +1079,7 @@ int bcr_solve(const double* Hb, const double* rhs, int32_t nv, int32_t W, int32_
         attrs = true;
     }
     // MFMA path (default) or the register elimination (SLAMHIP_BCR_LEGACY=1, A/B)
-    static const bool legacy = [] {
-        const char* e = getenv("SLAMHIP_BCR_LEGACY");
-        return e && e[0] == '1';
-    }();
+    const bool legacy = bcr_env_legacy();
     using OddMFn = void (*)(const double*, const double*, double*, double*, double*, double*, int32_t, int32_t,
                             int32_t, int32_t*);
     static const OddMFn odds_m[6] = {bcr_odd_mfma_kernel<1>, bcr_odd_mfma_kernel<2>, bcr_odd_mfma_kernel<3>,
@@ -1087,10 +1093,7 @@ int bcr_solve(const double* Hb, const double* rhs, int32_t nv, int32_t W, int32_
     // the odd blocks' blocked MFMA elimination (SLAMHIP_BCR_ODD_MFMA=1) is kept
     // for A/B: its single-wave panel factorization is slower than the register
     // elimination today
-    static const bool odd_mfma = [] {
-        const char* e = getenv("SLAMHIP_BCR_ODD_MFMA");
-        return e && e[0] == '1';
-    }();
+    const bool odd_mfma = bcr_env_odd_mfma();
     static bool attrs_m = false;
     if (!attrs_m) {
         for (int t = 0; t < 6; ++t) {

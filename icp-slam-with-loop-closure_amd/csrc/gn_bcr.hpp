@@ -36,6 +36,14 @@ struct BcrSchur {
     double* xb;             // nbd: the border's solution
     int32_t* status;        // the iteration's status word (a fused wait that timed out sets 2)
 };
+// The A/B switches of the cyclic reduction, each read from the environment at
+// its first use (the fused default: when the library loads) and latched for
+// the process (slam_gn_bcr_variant reports them).
+bool bcr_env_chol();       // SLAMHIP_BCR_CHOL=1: the Cholesky paths (MFMA even / top kernels)
+bool bcr_env_legacy();     // SLAMHIP_BCR_LEGACY=1: the register-elimination kernels
+bool bcr_env_odd_mfma();   // SLAMHIP_BCR_ODD_MFMA=1: bcr_odd_mfma_kernel on the Cholesky path
+int bcr_gj_env_split_min();    // SLAMHIP_GN_SPLIT_MIN=n: levels of >= n odd blocks pre-invert (0: never)
+int bcr_gj_env_fused();        // SLAMHIP_GN_FUSED_BACK=0: the fused back-substitution's default is off
 // The XCD-local fused back-substitution on (1, default) or off (0).
 void bcr_gj_set_fused(int on);
 int bcr_gj_get_fused();

@@ -1238,6 +1238,20 @@ constexpr int kBcrGjSlots = 2 * 256;   // odd-kernel workgroups resident at once
 // 1-2 costs 2-4 %: 5,340-5,347 it/s unsplit against 5,240-5,271 / 5,094-5,211,
 // bit-identical chi2; profiles/r06_gn_ab_split.txt)
 constexpr int kGjSplitMin = 0;
+int bcr_gj_env_split_min() {
+    static const int n = [] {
+        const char* e = getenv("SLAMHIP_GN_SPLIT_MIN");
+        return e ? atoi(e) : kGjSplitMin;
+    }();
+    return n;
+}
+int bcr_gj_env_fused() {   // default on; SLAMHIP_GN_FUSED_BACK=0 turns it off
+    static const int on = [] {
+        const char* e = getenv("SLAMHIP_GN_FUSED_BACK");
+        return e && e[0] == '0' ? 0 : 1;
+    }();
+    return on;
+}
 
 BcrGjBufs bcr_gj_bufs(double* work, int32_t nv, int32_t Wb, int32_t mc) {
     const int64_t nb = (nv + Wb - 1) / Wb;
@@ -1282,10 +1296,7 @@ int bcr_gj_levels(const BcrGjBufs& b, int32_t nv, int32_t Wb, int32_t mc, int32_
                                   bcrgj::inv_kernel<4>, bcrgj::inv_kernel<5>, bcrgj::inv_kernel<6>};
     // levels with at least this many odd blocks invert them once (inv_kernel),
     // before the products (SLAMHIP_GN_SPLIT_MIN=n selects it for A/B; 0 = never)
-    static const int split_min = [] {
-        const char* e = getenv("SLAMHIP_GN_SPLIT_MIN");
-        return e ? atoi(e) : kGjSplitMin;
-    }();
+    const int split_min = bcr_gj_env_split_min();
     static const OddFn odds[6] = {bcrgj::odd_kernel<1>, bcrgj::odd_kernel<2>, bcrgj::odd_kernel<3>,
                                   bcrgj::odd_kernel<4>, bcrgj::odd_kernel<5>, bcrgj::odd_kernel<6>};
     static const size_t lds1[6] = {bcrgj::Lds<1>::bytes, bcrgj::Lds<2>::bytes, bcrgj::Lds<3>::bytes,
@@ -1393,10 +1404,7 @@ int bcr_border_solve(const double* Z, const double* BR, const double* rhs, const
     return check_launch("gn border solve");
 }
 
-static int g_fused = [] {   // default on; SLAMHIP_GN_FUSED_BACK=0 turns it off
-    const char* e = getenv("SLAMHIP_GN_FUSED_BACK");
-    return e && e[0] == '0' ? 0 : 1;
-}();
+static int g_fused = bcr_gj_env_fused();
 static uint32_t g_fused_wait = 20000000;   // 0.2 s of s_memrealtime ticks per wait
 void bcr_gj_set_fused(int on) { g_fused = on ? 1 : 0; }
 int bcr_gj_get_fused() { return g_fused; }

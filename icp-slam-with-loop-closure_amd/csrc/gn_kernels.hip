@@ -923,6 +923,15 @@ extern "C" {
 
 int slam_gn_schur_supported(void) { return g_gn_solver != 1 && bcr_gj_default() ? 1 : 0; }
 
+// Diagnostics (host only): the cyclic reduction's A/B switches as this process
+// latched them from the environment.
+int slam_gn_bcr_variant(void) {
+    return (bcr_env_chol() ? SLAM_GN_VARIANT_CHOL : 0) | (bcr_env_legacy() ? SLAM_GN_VARIANT_LEGACY : 0) |
+           (bcr_env_odd_mfma() ? SLAM_GN_VARIANT_ODD_MFMA : 0) |
+           (bcr_gj_env_split_min() > 0 ? SLAM_GN_VARIANT_SPLIT : 0) |
+           (bcr_gj_env_fused() ? SLAM_GN_VARIANT_FUSED_BACK : 0);
+}
+
 int slam_gn_iteration_f64(double* poses, int32_t N, const int32_t* ea, const int32_t* eb, const double* tf,
                           const double* w, int32_t E, const int32_t* node_col, const int32_t* slot_rc,
                           const int32_t* slot_ptr, const int32_t* slot_items, int32_t n_slots, int32_t nv,

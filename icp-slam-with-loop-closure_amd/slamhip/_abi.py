@@ -87,7 +87,11 @@ SIGNATURES = {
     "slam_gn_get_fused_back": (c_int, []),
     "slam_gn_schur_supported": (c_int, []),
     "slam_gn_set_fused_wait": (c_int, [ctypes.c_uint32]),
+    "slam_gn_bcr_variant": (c_int, []),
 }
+
+# bits of slam_gn_bcr_variant() (SLAM_GN_VARIANT_* in include/slamhip.h)
+GN_VARIANT_CHOL, GN_VARIANT_LEGACY, GN_VARIANT_ODD_MFMA, GN_VARIANT_SPLIT, GN_VARIANT_FUSED_BACK = 1, 2, 4, 8, 16
 
 
 class SlamHipError(RuntimeError):

@@ -232,6 +232,25 @@ int slam_gn_get_fused_back(void);
  * switches), 0 otherwise: a bordered plan then takes
  * slam_gn_iteration_bordered_f64. */
 int slam_gn_schur_supported(void);
+/* Diagnostics (host only; new since ABI 102): which of the cyclic reduction's
+ * A/B switches this process latched from its environment, as a bitmask.  Each
+ * switch is read once, at its first use or at this call, whichever is first:
+ *   SLAM_GN_VARIANT_CHOL        SLAMHIP_BCR_CHOL=1 (Cholesky paths)
+ *   SLAM_GN_VARIANT_LEGACY      SLAMHIP_BCR_LEGACY=1 (register elimination)
+ *   SLAM_GN_VARIANT_ODD_MFMA    SLAMHIP_BCR_ODD_MFMA=1 (blocked MFMA odd kernel)
+ *   SLAM_GN_VARIANT_SPLIT       SLAMHIP_GN_SPLIT_MIN=n with n > 0 (levels of at
+ *                               least n odd blocks invert them once, in place)
+ *   SLAM_GN_VARIANT_FUSED_BACK  the fused back-substitution's default is on
+ *                               (off with SLAMHIP_GN_FUSED_BACK=0;
+ *                               slam_gn_set_fused_back changes the current
+ *                               setting, not this bit)
+ * A default process returns SLAM_GN_VARIANT_FUSED_BACK. */
+#define SLAM_GN_VARIANT_CHOL 1
+#define SLAM_GN_VARIANT_LEGACY 2
+#define SLAM_GN_VARIANT_ODD_MFMA 4
+#define SLAM_GN_VARIANT_SPLIT 8
+#define SLAM_GN_VARIANT_FUSED_BACK 16
+int slam_gn_bcr_variant(void);
 /* Diagnostics: the fused back-substitution's longest wait in s_memrealtime
  * ticks (0: the default 0.2 s); a tiny wait forces the timeout path. */
 int slam_gn_set_fused_wait(uint32_t ticks);

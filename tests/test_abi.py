@@ -58,3 +58,9 @@ def test_host_only_calls():
     i = lib.slam_icp_selected_instance(1081)
     assert lib.slam_icp_instance_shape(i, ctypes.byref(b), ctypes.byref(q)) == 0
     assert b.value * q.value >= 1081
+    # the cyclic reduction's latched A/B switches: none of them set in the
+    # environment leaves the fused back-substitution's default bit alone
+    if not any(k.startswith(("SLAMHIP_BCR_", "SLAMHIP_GN_")) for k in os.environ):
+        assert lib.slam_gn_bcr_variant() == _abi.GN_VARIANT_FUSED_BACK
+        assert lib.slam_gn_schur_supported() == 1
+    assert lib.slam_gn_bcr_variant() == lib.slam_gn_bcr_variant()

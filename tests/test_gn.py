@@ -127,14 +127,26 @@ def test_oracle_converges_on_c4():
 @pytest.mark.parametrize("iters", [1, 3])
 @pytest.mark.parametrize("mode", [1, 2])
 def test_gn_small_vs_oracle(solver, iters, mode):
-    from slamhip import gn
+    """The random graph's plan has W = 68 (80-row blocks, 3 of them): below
+    the reduction's 4-block threshold, so mode 2 runs the band Cholesky on it
+    too.  Mode 2 therefore takes a second graph that does reach the cyclic
+    reduction (gn_step.py's N49_d10: 5 blocks of 32 rows)."""
+    import gn_step as gs
+    from slamhip import _abi, gn
     solver(mode)
     guess, ea, eb, tf = _random_graph(80, 30, 2)
-    ref, ref_chi = go.optimize(guess, ea, eb, tf, iterations=iters)
-    got, chi = gn.optimize(guess, ea, eb, tf, iterations=iters)
-    assert np.allclose(chi, ref_chi, rtol=1e-9, atol=1e-9)
-    assert np.abs(got[:, :2] - ref[:, :2]).max() <= 1e-8
-    assert np.abs(go.wrap(got[:, 2] - ref[:, 2])).max() <= 1e-8
+    graphs = [(guess, ea, eb, tf, None)]
+    if mode == 2:
+        case = gs.BY_NAME["N49_d10"]
+        plan = gs.case_plan(case)
+        assert _abi.lib().slam_gn_bcr_block_rows(plan.nv_band, plan.W) == case.wb == 32
+        graphs.append(tuple(np.array(a) for a in gs.case_graph(case)) + (plan,))
+    for guess, ea, eb, tf, plan in graphs:
+        ref, ref_chi = go.optimize(guess, ea, eb, tf, iterations=iters)
+        got, chi = gn.optimize(guess, ea, eb, tf, iterations=iters, plan=plan)
+        assert np.allclose(chi, ref_chi, rtol=1e-9, atol=1e-9)
+        assert np.abs(got[:, :2] - ref[:, :2]).max() <= 1e-8
+        assert np.abs(go.wrap(got[:, 2] - ref[:, 2])).max() <= 1e-8
 
 
 @pytest.fixture
@@ -253,9 +265,11 @@ def test_gn_narrow_band(solver, n_nodes, mode):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(25, 3, 200), (40, 4, 500), (25, 6, 400), (30, 8, 800), (60, 12, 2000)])
 def test_gn_bcr_block_sizes(shape):
-    """Lap graphs whose RCM bands give cyclic-reduction blocks of 32, 48, 64
-    and 96 rows (register tiles 2..6), and one too wide for it (W = 125 ->
-    band Cholesky): both paths against the oracle."""
+    """Lap graphs whose default plans (RCM, or place-major with a border of
+    9, 15 and 24 scalars) give cyclic-reduction blocks of 32, 32, 48 and 64
+    rows (register tiles 2..4), and one too wide for it (W = 125 -> band
+    Cholesky): both paths against the oracle.  Blocks of 80 and 96 rows
+    (tiles 5 and 6) are covered by tests/test_gn_step_gpu.py."""
     from slamhip import _abi, gn, synthetic
     pps, nl, nloops = shape
     guess, ea, eb, tf, truth = synthetic.lap_graph_c4(poses_per_side=pps, num_loops=nl, n_loops=nloops)
