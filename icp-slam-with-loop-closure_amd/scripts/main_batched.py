@@ -19,6 +19,11 @@ loop pairs.  ``--loop-closure-init csm`` (new, opt-in) starts every
 loop-closure ICP from the batched correlative scan match of its pair
 (slamhip.csm) instead of the reference's identity; ``--csm-window-m``,
 ``--csm-angle-window-deg`` and ``--csm-angle-step-deg`` size its search.
+``--loop-closure-detection proximity`` (new, opt-in; used when no manual file
+is given) finds the loop closures itself: the reference's ``detect_proximity``
+with the candidate search on the GPU (slamhip.lcd) and the candidates' ICP on
+the resident scans; ``--proximity-min-dist-along-path``, ``--proximity-max-dist``
+and ``--proximity-icp-error`` default to the reference's 2 / 1 / 110.
 Out of scope here (flags accepted, ignored): image-based loop
 closure detection (OpenCV) and the matplotlib figures.
 
@@ -58,6 +63,15 @@ def parse(argv=None):
                    help="accepted for compatibility; the manual path uses the reference's fixed 30")
     p.add_argument("--loop-closure-init", default="identity", choices=["identity", "csm"],
                    help="identity = the reference's ICP start (default); csm = correlative scan match of every pair")
+    p.add_argument("--loop-closure-detection", default="none", choices=["none", "proximity"],
+                   help="without --manual-loop-closures: none (default), or proximity = the reference's "
+                        "detect_proximity with the candidate search on the GPU")
+    p.add_argument("--proximity-min-dist-along-path", default=2, type=float,
+                   help="proximity: least path length between the two poses of a candidate (m)")
+    p.add_argument("--proximity-max-dist", default=1, type=float,
+                   help="proximity: largest distance between the two poses of a candidate (m)")
+    p.add_argument("--proximity-icp-error", default=110, type=float,
+                   help="proximity: a candidate is accepted below this ICP error")
     p.add_argument("--csm-window-m", default=1.5, type=float,
                    help="csm: half-width of the shift search (m), in cells of 0.05 m")
     p.add_argument("--csm-angle-window-deg", default=180.0, type=float, help="csm: half-width of the angle search")
@@ -156,7 +170,15 @@ def run(a):
         pg = pose_graph.PoseGraph(None)
         pg.load(a.pose_graph)
     if a.program_start in ("scan_matching", "loop_closure"):
-        if a.manual_loop_closures is None:
+        if a.manual_loop_closures is None and a.loop_closure_detection == "proximity":
+            t0 = time.perf_counter()
+            cand, ok = pipeline.proximity_loop_closures(
+                pg, scans, a.proximity_min_dist_along_path, a.proximity_max_dist, a.proximity_icp_error,
+                init=a.loop_closure_init, csm=csm_params(a) if a.loop_closure_init == "csm" else None)
+            report["loop_closure_detection"] = {"method": "proximity", "candidates": len(cand),
+                                                "accepted": int(ok.sum()), "init": a.loop_closure_init,
+                                                "s": round(time.perf_counter() - t0, 3)}
+        elif a.manual_loop_closures is None:
             print("image-based loop closure detection needs OpenCV (out of scope); no loop closures added",
                   file=sys.stderr)
         else:

@@ -9,7 +9,9 @@ The reference runs its hot path from ``scripts/main.py``:
 * stage 2, manual loop closures (``scripts/main.py:298-307``): ``icp.icp``
   with an identity init for every annotated (i, j); the constraint is added
   when the returned error is below 30 (image-based detection needs OpenCV and
-  stays out of scope);
+  stays out of scope); or, opt-in, the reference's lidar-only detector
+  (``src/loop_closure_detection.py:11-39``) with its candidate search on the
+  GPU (``proximity_loop_closures``);
 * stage 3, optimisation (``scripts/main.py:322-334``): ``optimization_max_iters``
   SGD steps with learning rate 1/(k+1), then the orientation recompute.
 
@@ -110,6 +112,44 @@ def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
         if good:
             add_loop_constraint(pg, int(i), int(j), t.copy(), "icp")   # icp(pc_i, pc_j): X_i = X_j T
     return ok
+
+
+def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110, max_iters=100,
+                            epsilon=0.05, scanset=None, init="identity", csm=None):
+    """Stage 2 without annotations: the reference's ``detect_proximity``
+    (``src/loop_closure_detection.py:11-39``) on resident data.  The candidate
+    pairs come from the GPU search of ``slamhip.lcd`` (the nearest pose at
+    least ``min_dist_along_path`` further along the path, within ``max_dist``;
+    O(N) memory), every candidate's icp(pc_j, pc_i) runs in ONE launch over
+    the resident ``scanset`` by index (no second upload of the scans), and the
+    reference's greedy pass is replayed on the results: reverse order, each
+    node used once, ``error < err_thresh``, the constraint in the "relative"
+    convention.  ``init="csm"`` starts every ICP from the correlative scan
+    match of its pair.  Returns the candidates, a list of (i, j) in the order
+    the pass visits them, and the boolean mask of those accepted."""
+    from . import icp as _icp
+    from . import lcd as _lcd
+    check_loop_closure_init(init)
+    cand = _lcd.proximity_candidates_device(pg.poses, min_dist_along_path, max_dist)
+    accepted = np.zeros(len(cand), dtype=bool)
+    if not cand:
+        return cand, accepted
+    pairs = np.asarray(cand, dtype=np.int64)
+    ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
+    src, dst = pairs[:, 1], pairs[:, 0]   # icp(pc_j, pc_i), reference :33-35
+    batch = _icp.IcpBatch(ss, src, dst, loop_closure_inits(ss, src, dst, init, csm), epsilon=epsilon,
+                          max_iters=max_iters)
+    batch.launch()
+    r = batch.result()
+    used = set()
+    for b, (i, j) in enumerate(cand):
+        if i in used or j in used:
+            continue
+        if float(r.err[b]) < err_thresh:
+            add_loop_constraint(pg, i, j, r.tf[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
+            used.update((i, j))
+            accepted[b] = True
+    return cand, accepted
 
 
 def add_loop_constraint(pg, i, j, T, convention):

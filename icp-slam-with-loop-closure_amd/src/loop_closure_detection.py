@@ -24,7 +24,10 @@ New, opt-in (a trailing keyword of both functions; the reference's call shapes
 bind unchanged): ``init="csm"`` starts every ICP from the batched correlative
 scan match of its pair (``slamhip.csm``; ``csm``: its ``CsmParams``) instead
 of the identity, for loops closed at another heading.  The default
-``init="identity"`` is the reference's behaviour.
+``init="identity"`` is the reference's behaviour.  ``detect_proximity`` also
+takes ``candidates="device"``: the same candidate pairs from the GPU search of
+``slamhip.lcd`` (O(N) memory) instead of the N x N ``cdist`` matrix of the
+default ``candidates="host"``.
 """
 import numpy as np
 import scipy.spatial
@@ -79,9 +82,15 @@ def proximity_candidates(poses, min_dist_along_path=2, max_dist=1):
 
 
 def detect_proximity(pose_graph, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110,
-                     init="identity", csm=None):
+                     init="identity", csm=None, candidates="host"):
     check_loop_closure_init(init)
-    cand = proximity_candidates(pose_graph.poses, min_dist_along_path, max_dist)
+    if candidates == "host":
+        cand = proximity_candidates(pose_graph.poses, min_dist_along_path, max_dist)
+    elif candidates == "device":
+        from slamhip.lcd import proximity_candidates_device
+        cand = proximity_candidates_device(pose_graph.poses, min_dist_along_path, max_dist)
+    else:
+        raise ValueError(f"unknown candidate search {candidates!r} (host | device)")
     if not cand:
         return
     # icp(pc_j, pc_i) for every candidate, one launch (reference :33-35)

@@ -313,6 +313,32 @@ int slam_csm_batch(const double* pts, const int64_t* scan_off, const int32_t* sr
  * results. */
 int slam_csm_set_gather(int width);
 
+/* ---- proximity loop-closure candidates (csrc/lcd_kernels.hip) --------------
+ * The candidate search of src/loop_closure_detection.py:12-24
+ * (detect_proximity): for every pose the nearest pose far enough along the
+ * path, start[i] + np.argmin(cdist(xy, xy)[i, start[i]:]), without the N x N
+ * matrix; new since ABI 103.
+ *   poses     float64[N][3]  (x, y, theta; theta unused), finite
+ *   start     int32[n_rows]  first admissible column of row i, 0 <= start[i]
+ *             < N (the caller's np.searchsorted over the walked path length)
+ *   n_rows    rows searched, n_rows <= N
+ * For row i and column j: dx = x_i - x_j, dy = y_i - y_j, s = (dx dx) +
+ * (dy dy) with three roundings (no FMA contraction), d(i, j) = sqrt(s)
+ * correctly rounded.  out_j[i] is the SMALLEST j in [start[i], N) whose
+ * d(i, j) is minimal and out_d[i] that d.  Ties are ties of the rounded
+ * square roots, not of s: two different s may round to the same d, and the
+ * earlier column wins even when its s is larger.  Partial results are merged
+ * lexicographically on (d, j); no floating-point atomics: the result does not
+ * depend on the launch shape.
+ *   out_j     int32[n_rows]
+ *   out_d     float64[n_rows]
+ *   work      slam_lcd_work_size(N) BYTES, linear in N (at most 192 per pose)
+ * SLAM_EINVAL for a null array, N <= 0, n_rows < 0 or n_rows > N
+ * (slam_lcd_work_size: for N <= 0); n_rows == 0 succeeds without a launch. */
+int64_t slam_lcd_work_size(int32_t N);
+int slam_lcd_nearest_f64(const double* poses, int32_t N, const int32_t* start, int32_t n_rows, int32_t* out_j,
+                         double* out_d, void* work, void* stream);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
