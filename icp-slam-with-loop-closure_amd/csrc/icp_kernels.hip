@@ -3498,7 +3498,7 @@ using namespace slamhip;
 
 extern "C" {
 
-int slam_abi_version(void) { return 103; }
+int slam_abi_version(void) { return 104; }
 
 const char* slam_last_error(void) { return last_error_buf(); }
 

@@ -24,8 +24,18 @@ is given) finds the loop closures itself: the reference's ``detect_proximity``
 with the candidate search on the GPU (slamhip.lcd) and the candidates' ICP on
 the resident scans; ``--proximity-min-dist-along-path``, ``--proximity-max-dist``
 and ``--proximity-icp-error`` default to the reference's 2 / 1 / 110.
-Out of scope here (flags accepted, ignored): image-based loop
-closure detection (OpenCV) and the matplotlib figures.
+``--loop-closure-detection descriptors`` (new, opt-in) is the reference's image
+detector from the ORB descriptors on: ``--descriptors FILE.npz`` (arrays
+``desc`` uint8 (D, 32) and ``off`` int64 (M + 1); image m belongs to scan
+m * ``--image-downsample``), or ``--descriptors auto`` for a synthetic loop
+dataset (slamhip.synthetic.make_descriptors); every image pair is matched on
+the GPU (slamhip.desc, ``--descriptor-metric hamming|l2``), then the
+reference's selection and one ICP launch.  ``--image-match-error``,
+``--keypoint-n-matches``, ``--image-downsample`` and ``--min-dist-along-path``
+feed it (scripts/main.py's defaults 2500 / 20 / 1 / 5 when unset) and
+``--loop-closure-icp-error`` is its ICP threshold.
+Out of scope here (flags accepted, ignored): ORB keypoint extraction from
+images (OpenCV) and the matplotlib figures.
 
     python icp-slam-with-loop-closure_amd/scripts/main_batched.py synthetic:loop:2000:3 \\
         --manual-loop-closures auto --results-dir /tmp/results
@@ -60,12 +70,19 @@ def parse(argv=None):
     p.add_argument("--manual-loop-closures",
                    help="text file of (i, j) rows, or 'auto' for a synthetic loop dataset's ground truth")
     p.add_argument("--loop-closure-icp-error", default=30, type=float,
-                   help="accepted for compatibility; the manual path uses the reference's fixed 30")
+                   help="descriptors: a selected pair is accepted below this ICP error; the manual path uses the "
+                        "reference's fixed 30")
     p.add_argument("--loop-closure-init", default="identity", choices=["identity", "csm"],
                    help="identity = the reference's ICP start (default); csm = correlative scan match of every pair")
-    p.add_argument("--loop-closure-detection", default="none", choices=["none", "proximity"],
-                   help="without --manual-loop-closures: none (default), or proximity = the reference's "
-                        "detect_proximity with the candidate search on the GPU")
+    p.add_argument("--loop-closure-detection", default="none", choices=["none", "proximity", "descriptors"],
+                   help="without --manual-loop-closures: none (default), proximity = the reference's "
+                        "detect_proximity with the candidate search on the GPU, or descriptors = its image "
+                        "detector from the ORB descriptors on, matched on the GPU")
+    p.add_argument("--descriptors", help="descriptors: an .npz with desc (D, 32) uint8 and off (M + 1) int64, or "
+                                         "'auto' for a synthetic loop dataset")
+    p.add_argument("--descriptor-metric", default="hamming", choices=["hamming", "l2"],
+                   help="descriptors: hamming = cross-checked brute force (default), l2 = the exact search the "
+                        "reference's FLANN matcher approximates")
     p.add_argument("--proximity-min-dist-along-path", default=2, type=float,
                    help="proximity: least path length between the two poses of a candidate (m)")
     p.add_argument("--proximity-max-dist", default=1, type=float,
@@ -86,7 +103,7 @@ def parse(argv=None):
     p.add_argument("--miss-odds", default=2, type=int)
     for f in ("--produce-odometry-map", "--skip-occupancy-grid", "--save-map-files", "--occupancy-grid-mle"):
         p.add_argument(f, action="store_true")
-    # reference flags for figures / image matching: accepted, not used here
+    # reference flags for figures (accepted, not used here) and image matching (--loop-closure-detection descriptors)
     for f, kw in (("--figure-dpi", dict(type=int)), ("--figure-width", dict(type=float)),
                   ("--figure-height", dict(type=float)), ("--image-downsample", dict(type=int)),
                   ("--image-match-error", dict(type=float)), ("--keypoint-n-matches", dict(type=int)),
@@ -99,6 +116,8 @@ def parse(argv=None):
         p.error("--program-end precedes --program-start")
     if a.program_start != "scan_matching" and not a.pose_graph:
         p.error("starting after scan matching needs --pose-graph")
+    if a.loop_closure_detection == "descriptors" and not a.descriptors:
+        p.error("--loop-closure-detection descriptors needs --descriptors FILE.npz (or auto)")
     if not (a.csm_window_m >= 0 and 0 < a.csm_angle_step_deg and 0 <= a.csm_angle_window_deg <= 180):
         p.error("--csm-window-m >= 0, --csm-angle-step-deg > 0 and 0 <= --csm-angle-window-deg <= 180 expected")
     return a
@@ -112,6 +131,31 @@ def csm_params(a):
     side = 2 * int(round(a.csm_window_m / res)) + 1
     n_theta = max(1, int(round(2 * a.csm_angle_window_deg / a.csm_angle_step_deg)))
     return CsmParams(res=res, n_theta=n_theta, d_theta=2 * np.pi / (360.0 / a.csm_angle_step_deg), nx=side, ny=side)
+
+
+IMAGE_DEFAULTS = dict(image_match_error=2500.0, keypoint_n_matches=20, image_downsample=1, min_dist_along_path=5)
+
+
+def image_params(a):
+    """The four image-matching flags, scripts/main.py's defaults where unset."""
+    return {k: (getattr(a, k) if getattr(a, k) is not None else v) for k, v in IMAGE_DEFAULTS.items()}
+
+
+def load_descriptors(a, n_scans, image_rate):
+    """One (n, 32) uint8 array per image: image m of scan m * image_rate of the
+    (sliced) dataset."""
+    if a.descriptors == "auto":
+        from slamhip import synthetic
+        parts = a.dataset.split(":")
+        if len(parts) < 3 or parts[:2] != ["synthetic", "loop"]:
+            raise SystemExit("--descriptors auto needs a synthetic:loop dataset")
+        seed = int(parts[3]) if len(parts) > 3 else 0
+        seq = synthetic.make_loop_sequence(int(parts[2]), seed=seed, n_beams=3)   # the lap layout only
+        per_scan = synthetic.make_descriptors(seq, seed)
+        return per_scan[a.dataset_start:a.dataset_start + n_scans][::image_rate]
+    with np.load(a.descriptors, allow_pickle=False) as z:
+        desc, off = z["desc"], z["off"]
+    return [desc[off[m]:off[m + 1]] for m in range(len(off) - 1)]
 
 
 def save_map(a, poses, scans, name, report):
@@ -178,8 +222,21 @@ def run(a):
             report["loop_closure_detection"] = {"method": "proximity", "candidates": len(cand),
                                                 "accepted": int(ok.sum()), "init": a.loop_closure_init,
                                                 "s": round(time.perf_counter() - t0, 3)}
+        elif a.manual_loop_closures is None and a.loop_closure_detection == "descriptors":
+            ip = image_params(a)
+            descriptors = load_descriptors(a, len(scans), ip["image_downsample"])
+            t0 = time.perf_counter()
+            good, ok = pipeline.image_loop_closures(
+                pg, scans, descriptors, ip["image_downsample"],
+                ip["min_dist_along_path"], ip["image_match_error"], ip["keypoint_n_matches"],
+                a.loop_closure_icp_error, metric=a.descriptor_metric, init=a.loop_closure_init,
+                csm=csm_params(a) if a.loop_closure_init == "csm" else None)
+            report["loop_closure_detection"] = {"method": "descriptors", "metric": a.descriptor_metric,
+                                                "selected": len(good), "accepted": int(ok.sum()),
+                                                "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
         elif a.manual_loop_closures is None:
-            print("image-based loop closure detection needs OpenCV (out of scope); no loop closures added",
+            print("image-based loop closure detection from images needs OpenCV (out of scope; see "
+                  "--loop-closure-detection descriptors); no loop closures added",
                   file=sys.stderr)
         else:
             if a.manual_loop_closures == "auto":

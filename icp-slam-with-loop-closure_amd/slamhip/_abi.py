@@ -75,6 +75,11 @@ SIGNATURES = {
     "slam_csm_set_gather": (c_int, [c_int]),
     "slam_lcd_work_size": (c_i64, [c_int]),
     "slam_lcd_nearest_f64": (c_int, [c_ptr, c_int, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "slam_desc_work_size": (c_i64, [c_int, c_int, c_int]),
+    "slam_desc_match_batch": (c_int, [c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr,
+                                      c_ptr, c_ptr]),
+    "slam_desc_status": (c_int, [c_ptr]),
+    "slam_desc_set_bwd": (c_int, [c_int]),
     "slam_gn_bcr_block_rows": (c_int, [c_int, c_int]),
     "slam_gn_iteration_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -8,10 +8,12 @@ The reference runs its hot path from ``scripts/main.py``:
   ``P_i = mat_to_pose(pose_to_mat(P_{i-1}) @ T_i)`` and a ``PoseGraph``;
 * stage 2, manual loop closures (``scripts/main.py:298-307``): ``icp.icp``
   with an identity init for every annotated (i, j); the constraint is added
-  when the returned error is below 30 (image-based detection needs OpenCV and
-  stays out of scope); or, opt-in, the reference's lidar-only detector
-  (``src/loop_closure_detection.py:11-39``) with its candidate search on the
-  GPU (``proximity_loop_closures``);
+  when the returned error is below 30; or, opt-in, the reference's lidar-only
+  detector (``src/loop_closure_detection.py:11-39``) with its candidate search
+  on the GPU (``proximity_loop_closures``); or, opt-in, its image detector
+  (``:81-163``) from the ORB descriptors on, every image pair matched on the
+  GPU (``image_loop_closures``; extracting the keypoints needs OpenCV and
+  stays out of scope);
 * stage 3, optimisation (``scripts/main.py:322-334``): ``optimization_max_iters``
   SGD steps with learning rate 1/(k+1), then the orientation recompute.
 
@@ -150,6 +152,55 @@ def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1,
             used.update((i, j))
             accepted[b] = True
     return cand, accepted
+
+
+def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path=5, image_err_thresh=125,
+                n_matches=10, icp_err_thresh=30, metric="hamming", scanset=None, init="identity", csm=None):
+    """``image_loop_closures`` with everything it computed: ``(good, accepted,
+    dist_mat, icp_result)`` (``icp_result`` None without a selected pair)."""
+    from . import desc as _desc
+    from . import icp as _icp
+    check_loop_closure_init(init)
+    ds = descriptors if isinstance(descriptors, _desc.DescriptorSet) else _desc.DescriptorSet(descriptors)
+    start = _desc.image_starts(pg.poses, min_dist_along_path, image_rate)
+    if len(start) != len(ds):
+        raise ValueError(f"{len(ds)} images for {len(pg.poses)} poses at image_rate {image_rate}: "
+                         f"expected {len(start)}")
+    dist_mat = _desc.similarity_matrix(ds, start, n_matches, metric)
+    good = _desc.select_matches(dist_mat, image_err_thresh)
+    accepted = np.zeros(len(good), dtype=bool)
+    if not good:
+        return good, accepted, dist_mat, None
+    pairs = np.asarray(good, dtype=np.int64) * int(image_rate)
+    ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
+    src, dst = pairs[:, 0], pairs[:, 1]   # icp(pc_i, pc_j), reference :136-142
+    batch = _icp.IcpBatch(ss, src, dst, loop_closure_inits(ss, src, dst, init, csm), epsilon=0.05, max_iters=100)
+    batch.launch()
+    r = batch.result()
+    accepted[:] = r.err < icp_err_thresh
+    for (i, j), t, ok in zip(pairs, r.tf, accepted):
+        if ok:
+            add_loop_constraint(pg, int(i), int(j), t.copy(), "icp")   # icp(pc_i, pc_j): X_i = X_j T
+    return good, accepted, dist_mat, r
+
+
+def image_loop_closures(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path=5,
+                        image_err_thresh=125, n_matches=10, icp_err_thresh=30,
+                        metric="hamming", scanset=None, init="identity", csm=None):
+    """Stage 2 from image descriptors: the reference's
+    ``detect_images_direct_similarity`` (``src/loop_closure_detection.py:84-159``)
+    after the keypoints.  ``descriptors``: one (n, 32) uint8 array per image
+    (image m belongs to scan m * ``image_rate``), or a resident
+    ``slamhip.desc.DescriptorSet``.  The starts (:84-91), every image pair
+    (i, j >= start[i]) matched on the GPU in one launch (``slamhip.desc``;
+    ``metric`` "hamming" is the reference's ``approximate_match=False``, "l2"
+    the exact search its default approximates), the column rule (:126-131),
+    icp(pc_i, pc_j) of every selected pair in ONE launch over the resident
+    ``scanset``, and the constraint where ``err < icp_err_thresh``, in the "icp"
+    convention.  Returns the selected (i, j) image pairs and the boolean mask of
+    those accepted."""
+    return image_stage(pg, lidar_points, descriptors, image_rate, min_dist_along_path, image_err_thresh, n_matches,
+                       icp_err_thresh, metric, scanset, init, csm)[:2]
 
 
 def add_loop_constraint(pg, i, j, T, convention):

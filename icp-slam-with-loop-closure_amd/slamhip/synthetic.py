@@ -305,3 +305,32 @@ def make_loop_sequence(n_scans: int, seed: int, n_beams=N_BEAMS, step=0.05, loop
     later = np.arange(per_lap, n_scans, loop_every)
     pairs = np.stack([later - per_lap, later], axis=1) if len(later) else np.zeros((0, 2), np.int64)
     return LoopSequence(world, truth, odom, scans, per_lap=per_lap, loop_pairs=pairs.astype(np.int64))
+
+
+def make_descriptors(seq: LoopSequence, seed: int, image_rate=1, n_per_image=500, shared=0.6, flip=12):
+    """Synthetic ORB-like descriptors for a loop sequence: one (n_per_image, 32)
+    uint8 array per image, image m taken at scan m * ``image_rate``.
+
+    Every lap position (scan index mod ``seq.per_lap``) owns a bank of
+    ``round(shared * n_per_image)`` random 256-bit codes.  An image shows its
+    position's bank with ``flip`` distinct random bits flipped in every
+    descriptor, plus random clutter up to ``n_per_image``, in shuffled order:
+    images of the same lap position match closely (about ``flip`` bits a
+    descriptor in each), any other two like random codes."""
+    per_lap = int(getattr(seq, "per_lap", 0))
+    if per_lap <= 0:
+        raise ValueError("make_descriptors needs a loop sequence (per_lap > 0)")
+    n_shared = int(round(shared * n_per_image))
+    if not 0 <= n_shared <= n_per_image or not 0 <= flip <= 256:
+        raise ValueError("0 <= shared <= 1 and 0 <= flip <= 256 expected")
+    out = []
+    for scan in range(0, len(seq.scans), int(image_rate)):
+        bank = np.random.default_rng([int(seed), 0, scan % per_lap]).integers(0, 256, (n_shared, 32), dtype=np.uint8)
+        rng = np.random.default_rng([int(seed), 1, scan])
+        bits = np.unpackbits(bank, axis=1)
+        which = np.argsort(rng.random((n_shared, 256)), axis=1)[:, :flip]
+        np.put_along_axis(bits, which, 1 - np.take_along_axis(bits, which, axis=1), axis=1)
+        clutter = rng.integers(0, 256, (n_per_image - n_shared, 32), dtype=np.uint8)
+        d = np.concatenate([np.packbits(bits, axis=1), clutter], axis=0)
+        out.append(np.ascontiguousarray(d[rng.permutation(len(d))]))
+    return out

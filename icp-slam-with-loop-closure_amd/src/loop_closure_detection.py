@@ -27,7 +27,13 @@ of the identity, for loops closed at another heading.  The default
 ``init="identity"`` is the reference's behaviour.  ``detect_proximity`` also
 takes ``candidates="device"``: the same candidate pairs from the GPU search of
 ``slamhip.lcd`` (O(N) memory) instead of the N x N ``cdist`` matrix of the
-default ``candidates="host"``.
+default ``candidates="host"``.  ``detect_images_direct_similarity`` takes
+``matcher="device"``: the descriptor matching (``slamhip.desc``, brute force on
+the GPU: ``approximate_match=True`` -> the exact ``l2`` search the FLANN kd-tree
+approximates, ``False`` -> cross-checked ``hamming``), the selection and the ICP
+run as ``slamhip.pipeline.image_loop_closures``; with ``descriptors=`` (one
+(n, 32) uint8 array per image) OpenCV is not needed at all.  The default
+``matcher="opencv"`` is the path above.
 """
 import numpy as np
 import scipy.spatial
@@ -150,8 +156,14 @@ def matchify(desc1, desc2, i, j, n_matches, approximate_match):
 def detect_images_direct_similarity(pose_graph, lidar_points, images, image_rate=1, min_dist_along_path=5,
                                     image_err_thresh=125, n_matches=10, icp_err_thresh=30, save_dists=False,
                                     save_matches=False, n_jobs=-1, approximate_match=True,
-                                    init="identity", csm=None):
+                                    init="identity", csm=None, matcher="opencv", descriptors=None):
     check_loop_closure_init(init)
+    if matcher == "device":
+        return _detect_images_device(pose_graph, lidar_points, images, image_rate, min_dist_along_path,
+                                     image_err_thresh, n_matches, icp_err_thresh, save_dists, save_matches, n_jobs,
+                                     approximate_match, init, csm, descriptors)
+    if matcher != "opencv":
+        raise ValueError(f"unknown matcher {matcher!r} (opencv | device)")
     cv2 = _cv2()
     from joblib import Parallel, delayed
     d, walked = _path_geometry(pose_graph.poses)
@@ -199,3 +211,53 @@ def detect_images_direct_similarity(pose_graph, lidar_points, images, image_rate
                 img = cv2.drawMatches(greys[i], keypoints[i0], greys[j], keypoints[j0], matched.get((i0, j0), []), None,
                                       flags=cv2.DrawMatchesFlags_NOT_DRAW_SINGLE_POINTS)
                 cv2.imwrite("results/match_%d_%d_%f.png" % (i, j, dist_mat[i0, j0]), img)
+
+
+def _save_dist_images(dist_mat, image_err_thresh):
+    import matplotlib.pyplot as plt
+    for img, name in ((dist_mat, "dist_mat"), (dist_mat < image_err_thresh, "dist_mat_threshed")):
+        fig, ax = plt.subplots()
+        ax.imshow(img)
+        plt.savefig("results/%s.png" % name)
+        plt.close(fig)
+
+
+def _detect_images_device(pose_graph, lidar_points, images, image_rate, min_dist_along_path, image_err_thresh,
+                          n_matches, icp_err_thresh, save_dists, save_matches, n_jobs, approximate_match, init, csm,
+                          descriptors):
+    """``matcher="device"``: the matching, the selection and the ICP of
+    ``slamhip.pipeline.image_loop_closures``.  With ``descriptors`` (one
+    (n, 32) uint8 array per image, image m of scan m * image_rate) OpenCV is
+    never imported; without them the ORB keypoints still come from it."""
+    from slamhip import desc as _desc
+    from slamhip.pipeline import image_stage
+    metric = "l2" if approximate_match else "hamming"
+    greys = keypoints = None
+    if descriptors is None:
+        cv2 = _cv2()
+        from joblib import Parallel, delayed
+        greys = [cv2.cvtColor(np.asarray(im, dtype=np.uint8), cv2.COLOR_RGB2GRAY) for im in images]
+        par = Parallel(n_jobs=n_jobs, verbose=0, backend="loky")
+        kps = par(delayed(find_keypoints)(greys[i]) for i in range(0, len(greys), image_rate))
+        keypoints, descriptors = zip(*[deserialize_keypoints(s) for s in kps])
+    elif save_matches:
+        raise ValueError("save_matches=True draws OpenCV keypoints: not available with descriptors= "
+                         "(pass save_matches=False, or images without descriptors)")
+    ds = descriptors if isinstance(descriptors, _desc.DescriptorSet) else _desc.DescriptorSet(descriptors)
+    good, accepted, dist_mat, _ = image_stage(pose_graph, lidar_points, ds, image_rate, min_dist_along_path,
+                                              image_err_thresh, n_matches, icp_err_thresh, metric, None, init, csm)
+    print("Closest images keypoint match error %f" % (np.min(dist_mat) if dist_mat.size else np.inf))
+    if save_dists:
+        _save_dist_images(dist_mat, image_err_thresh)
+    if save_matches and accepted.any():
+        cv2 = _cv2()
+        drawn = [g for g, ok in zip(good, accepted) if ok]
+        rows = _desc.match_pairs(ds, [i for i, _ in drawn], [j for _, j in drawn], n_matches, metric,
+                                 return_matches=True)[2]
+        for (i0, j0), m in zip(drawn, rows):
+            i, j = i0 * image_rate, j0 * image_rate
+            dm = [cv2.DMatch(int(a), int(b), float(np.sqrt(np.float32(d))) if approximate_match else float(d))
+                  for a, b, d in m]
+            img = cv2.drawMatches(greys[i], keypoints[i0], greys[j], keypoints[j0], dm, None,
+                                  flags=cv2.DrawMatchesFlags_NOT_DRAW_SINGLE_POINTS)
+            cv2.imwrite("results/match_%d_%d_%f.png" % (i, j, dist_mat[i0, j0]), img)

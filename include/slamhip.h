@@ -339,6 +339,64 @@ int64_t slam_lcd_work_size(int32_t N);
 int slam_lcd_nearest_f64(const double* poses, int32_t N, const int32_t* start, int32_t n_rows, int32_t* out_j,
                          double* out_d, void* work, void* stream);
 
+/* ---- binary-descriptor matching (csrc/desc_kernels.hip) ---------------------
+ * The hot loop of src/loop_closure_detection.py:61-79 (matchify), which
+ * detect_images_direct_similarity (:103) runs for every image pair: a
+ * brute-force match of two images' ORB descriptors and the sum of the
+ * n_matches best match distances; new since ABI 104.
+ *   desc      uint8[D][32]  all descriptors, 16-byte aligned; image m holds the
+ *             n_m >= 0 rows img_off[m] .. img_off[m + 1]
+ *   img_off   int64[M + 1]  ascending, img_off[M] <= D
+ *   qi, ti    int32[B]  query image (descriptors A) and train image (B) of pair b
+ *   metric    0 hamming, 1 l2
+ * hamming (cv2.BFMatcher(NORM_HAMMING, crossCheck=True).match(A, B), the
+ * reference's approximate_match=False): d(a, b) = popcount(A[a] xor B[b]) in
+ * 0..256; fwd[a] the smallest b with minimal d(a, .), bwd[b] the smallest a
+ * with minimal d(., b); the matches are {(a, fwd[a]) : bwd[fwd[a]] == a}.
+ * l2 (the exact search that the reference's default FLANN kd-tree
+ * approximates: bytes as float32, one way, no cross-check): d(a, b) =
+ * sum_c (A[a][c] - B[b][c])^2 as an integer, at most 2,080,800; the matches
+ * are (a, fwd[a]) for every a; the distance OpenCV reports is sqrtf(d).
+ * Both: the matches are ordered by (d, a) ascending (Python's stable
+ * sorted(matches, key=distance) of a query-ordered list); count is their
+ * number; the score is +inf when count < n_matches, otherwise the
+ * left-to-right float64 sum over the first n_matches matches of d (hamming,
+ * an exact integer) or of the float32 square root of d widened to float64
+ * (l2; the fp64 root rounded to float32 is the same float for every possible
+ * d, and distinct d have distinct roots).  An empty A or B gives count 0.
+ * The first-index tie rules are believed to be BFMatcher's; parity with
+ * OpenCV is unpinned.  Only integers decide the
+ * outcome: every launch shape gives the same bits.
+ *   out_score    float64[B]
+ *   out_count    int32[B]
+ *   out_matches  int32[B][n_matches][3] rows (a, b, d) of the first n_matches
+ *                matches, or NULL; the rows of a pair with count < n_matches
+ *                are filled with -1
+ *   work         slam_desc_work_size(B, max_n, n_matches) BYTES (max_n: the
+ *                most descriptors in one image); a pair's intermediates live
+ *                in its workgroup's LDS, so the size is a fixed 256 today
+ * Stream-ordered, graph-capturable, no host copies, nothing allocated.
+ * SLAM_EINVAL for a null array (other than out_matches), a desc pointer not
+ * 16-byte aligned, B < 0, M <= 0, an unknown metric or n_matches outside
+ * 1..256; B == 0 succeeds without a launch.  What only the device can see is
+ * checked there, pair by pair, like slam_icp_batch_f64's bounds: a pair that
+ * names an image outside [0, M) (or whose offsets descend), or an image of
+ * more than 4,096 descriptors, is not computed (out_score NaN, out_count -1,
+ * rows -1) and raises a flag.  slam_desc_status synchronises `stream` and
+ * reports the flag of every launch since the previous call, SLAM_OK,
+ * SLAM_EINVAL (a bad image index) or SLAM_ETOOBIG, and clears it.
+ * slam_desc_work_size returns SLAM_ETOOBIG for max_n > 4,096 itself. */
+int64_t slam_desc_work_size(int32_t B, int32_t max_n, int32_t n_matches);
+int slam_desc_match_batch(const uint8_t* desc, const int64_t* img_off, int32_t M, const int32_t* qi,
+                          const int32_t* ti, int32_t B, int32_t metric, int32_t n_matches, double* out_score,
+                          int32_t* out_count, int32_t* out_matches, void* work, void* stream);
+int slam_desc_status(void* stream);
+/* Diagnostics: how hamming finds bwd[b]: 0 (default) a second pass with the
+ * roles swapped, 1 one pass with an LDS integer atomicMin of the packed key
+ * d << 12 | a per distance (DESIGN.md section 3.7 has the A/B).  Per host
+ * thread; identical results. */
+int slam_desc_set_bwd(int mode);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
