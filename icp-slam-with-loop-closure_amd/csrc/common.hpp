@@ -295,4 +295,89 @@ __device__ __forceinline__ double wave_sum_exact16(double (&v)[16]) {
     return i == 0 ? t0 : i == 1 ? t1 : i == 2 ? t2 : t3;
 }
 
+// A float's bits as an int of the same order (sign-magnitude -> two's
+// complement, an involution; -0 < +0, no NaN inputs), and back.
+__device__ __forceinline__ int f2ord(float f) {
+    const int i = __float_as_int(f);
+    return i ^ ((i >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float ord2f(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
+
+// Signed maxima of 8 per-lane values over the wave's 64 lanes in ONE
+// reduce-scatter (the integer form of wave_sum_exact16; max is exact, so the
+// order is free): v_permlane32_swap on pairs (8 -> 4 registers: lanes 0-31
+// hold the even value over l, l+32, lanes 32-63 the odd one), v_permlane16_swap
+// (4 -> 2: row r of register i holds value 4 i + {0, 2, 1, 3}[r] over the four
+// rows), 4 DPP steps within the rows of the two survivors, and one v_readlane
+// per value: the results are wave-uniform (SGPRs).
+__device__ __forceinline__ void wave_max8_i32(int (&v)[8]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const auto p = __builtin_amdgcn_permlane32_swap(static_cast<unsigned>(v[2 * j]),
+                                                        static_cast<unsigned>(v[2 * j + 1]), false, false);
+        v[j] = max(static_cast<int>(p[0]), static_cast<int>(p[1]));
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const auto p = __builtin_amdgcn_permlane16_swap(static_cast<unsigned>(v[2 * i]),
+                                                        static_cast<unsigned>(v[2 * i + 1]), false, false);
+        v[i] = max(static_cast<int>(p[0]), static_cast<int>(p[1]));
+    }
+    int x0 = v[0], x1 = v[1];
+#define SLAM_DPPI(v, ctrl) __builtin_amdgcn_mov_dpp((v), (ctrl), 0xF, 0xF, true)
+    x0 = max(x0, SLAM_DPPI(x0, 0xB1));    // quad_perm [1,0,3,2]
+    x1 = max(x1, SLAM_DPPI(x1, 0xB1));
+    x0 = max(x0, SLAM_DPPI(x0, 0x4E));    // quad_perm [2,3,0,1]
+    x1 = max(x1, SLAM_DPPI(x1, 0x4E));
+    x0 = max(x0, SLAM_DPPI(x0, 0x124));   // row_ror:4
+    x1 = max(x1, SLAM_DPPI(x1, 0x124));
+    x0 = max(x0, SLAM_DPPI(x0, 0x128));   // row_ror:8
+    x1 = max(x1, SLAM_DPPI(x1, 0x128));
+#undef SLAM_DPPI
+    v[0] = __builtin_amdgcn_readlane(x0, 0);
+    v[2] = __builtin_amdgcn_readlane(x0, 16);
+    v[1] = __builtin_amdgcn_readlane(x0, 32);
+    v[3] = __builtin_amdgcn_readlane(x0, 48);
+    v[4] = __builtin_amdgcn_readlane(x1, 0);
+    v[6] = __builtin_amdgcn_readlane(x1, 16);
+    v[5] = __builtin_amdgcn_readlane(x1, 32);
+    v[7] = __builtin_amdgcn_readlane(x1, 48);
+}
+
+// Bounds of a 64-query group's active lanes for the ICP group search: the box
+// of their fp32 points, their largest M2 (non-negative or +inf: its bits order
+// as they are) and the intersection [wlo, whi) of their windows [ws, ws +
+// kwin).  All seven reduce as signed maxima of ordered 32-bit keys (the minima
+// complemented) in one wave_max8_i32; an inactive lane contributes each key's
+// identity (+-inf, 0, an empty intersection), so the results are the bits of
+// seven separate min / max reductions.  Wave-uniform; the key mapping is undone
+// on the scalar side.  At least one lane is active.
+struct GroupBounds {
+    float bx0, bx1, by0, by1, gM2;
+    int wlo, whi;
+};
+__device__ __forceinline__ GroupBounds wave_group_bounds(bool act, float qx, float qy, float M2, int ws, int kwin) {
+    const int ox = f2ord(qx), oy = f2ord(qy);
+    constexpr int kLo = static_cast<int>(0x807fffffu);   // f2ord(-inf): below every finite key
+    int v[8];
+    v[0] = act ? ~ox : kLo;           // ~f2ord(x) is decreasing in x, ~f2ord(+inf) = f2ord(-inf)
+    v[1] = act ? ox : kLo;
+    v[2] = act ? ~oy : kLo;
+    v[3] = act ? oy : kLo;
+    v[4] = act ? __float_as_int(M2) : 0;
+    v[5] = act ? ws : 0;
+    v[6] = act ? 0xffff - (ws + kwin) : 0;
+    v[7] = 0;
+    wave_max8_i32(v);
+    GroupBounds g;
+    g.bx0 = ord2f(~v[0]);
+    g.bx1 = ord2f(v[1]);
+    g.by0 = ord2f(~v[2]);
+    g.by1 = ord2f(v[3]);
+    g.gM2 = __int_as_float(v[4]);
+    g.wlo = v[5];
+    g.whi = 0xffff - v[6];
+    return g;
+}
+
 }  // namespace slamhip

@@ -273,11 +273,7 @@ __device__ __forceinline__ void trace_mark(const IcpArgs& a, int b, int what) {
 // order as their unsigned bits.  An integer min takes the DPP operand directly
 // (v_min_i32_dpp, bound_ctrl: one instruction per step), where fminf would
 // canonicalise both operands first (IEEE mode) behind a separate DPP move.
-__device__ __forceinline__ int f2ord(float f) {
-    const int i = __float_as_int(f);
-    return i ^ ((i >> 31) & 0x7fffffff);
-}
-__device__ __forceinline__ float ord2f(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
+// (f2ord / ord2f: common.hpp)
 #define SLAM_DPPI(v, ctrl) __builtin_amdgcn_mov_dpp((v), (ctrl), 0xF, 0xF, true)
 template <typename I, typename Op>
 __device__ __forceinline__ I wave_reduce_i(I v, Op op) {
@@ -361,6 +357,13 @@ constexpr int kSub = 8;
 #ifndef SLAM_KBATCH
 #define SLAM_KBATCH 4   // round 5, after the windows' intersection left the live sets: 4 for 3 (10k bench
                         // 4.00-4.03 ms against 4.06-4.07; 2: 4.21-4.23, 5 / 6: 4.07; profiles/r05_ab_kbatch*.txt)
+#endif
+#ifndef SLAM_GS_FUSED
+#define SLAM_GS_FUSED 1   // group search: the group's bounds in one fused reduction (wave_group_bounds) for
+                          // six; 0: the round-6 form.  10k bench 3.92-3.95 ms against 3.97-3.99, -3.1 % VALU
+                          // instructions: 1.8-2.8 times the parent's run-to-run range, under the factor 3 set
+                          // for keeping a part; kept because no run overlaps (profiles/r07_ab_group_search.txt,
+                          // DESIGN.md section 3.1)
 #endif
 constexpr int kWin = SLAM_KWIN;  // window sub-chunks (32 candidates); 2/5/6/8 measured slower
 constexpr int kStageUnroll = 4;  // staging loads in flight per thread
@@ -537,6 +540,20 @@ __device__ __forceinline__ void nn_window_pruned(const float2* __restrict__ cand
                 f0 = f1;
             }
         };
+#if SLAM_GS_FUSED
+        // one reduce-scatter over ordered keys for the box, the largest M2 and the
+        // windows' intersection: the same bits as the separate reductions below
+        const GroupBounds gb = wave_group_bounds(act[k], qx[k], qy[k], M2[k], ws[k], kWin);
+        const float bx0 = gb.bx0, bx1 = gb.bx1, by0 = gb.by0, by1 = gb.by1, gM2 = gb.gM2;
+#ifndef SLAM_NO_WINX
+        // sub-chunks inside EVERY active lane's window ([wlo, whi): the windows'
+        // intersection) are needed by no active lane and bound nothing it needs
+        // (the clearance covers the candidates outside its own window): not live
+        const int wlo = gb.wlo, whi = gb.whi;
+#else
+        const int wlo = 0, whi = 0;
+#endif
+#else
         const float bx0 = wave_min_f(act[k] ? qx[k] : INFINITY);
         const float bx1 = wave_max_f(act[k] ? qx[k] : -INFINITY);
         const float by0 = wave_min_f(act[k] ? qy[k] : INFINITY);
@@ -552,6 +569,7 @@ __device__ __forceinline__ void nn_window_pruned(const float2* __restrict__ cand
         const int wlo = static_cast<int>(wx >> 16), whi = 0xffff - static_cast<int>(wx & 0xffff);
 #else
         const int wlo = 0, whi = 0;
+#endif
 #endif
         float gf = INFINITY, lmin = INFINITY;
         flap(5);
@@ -2443,7 +2461,10 @@ static const Instance kInstances[] = {
     SLAM_INST(64, 1, 1),   SLAM_INST(64, 2, 1),   SLAM_INST(64, 4, 1),   SLAM_INST(128, 3, 1),
     SLAM_INST(128, 4, 1),  SLAM_INST(192, 4, 1),  SLAM_INST(192, 6, 1),  SLAM_INST(256, 4, 1),
     SLAM_INST(256, 5, kWpe), SLAM_INST(320, 4, 1),  SLAM_INST(384, 3, 1),  SLAM_INST(512, 3, 1),
-    SLAM_INST(576, 2, 1),  SLAM_INST(512, 4, 1),  SLAM_INST(512, 6, 1),  SLAM_INST(512, 8, 1),
+    // 512x4 (scans of 1,537-2,048 points): held to 128 VGPRs like 256x5 — uncapped it compiles to 129 with the
+    // fused group reduction (127 before), one 8-wave workgroup per CU instead of two: 5.9-6.0 ms against 4.8-4.9
+    // on 3,000 pairs of 1,800 points (profiles/r07_ab_beams1800.txt)
+    SLAM_INST(576, 2, 1),  SLAM_INST(512, 4, kWpe),  SLAM_INST(512, 6, 1),  SLAM_INST(512, 8, 1),
     SLAM_INST(512, 16, 1),
 };
 #undef SLAM_INST
