@@ -87,17 +87,15 @@ __device__ __forceinline__ SE2 se2_mul(const SE2& a, const SE2& b) {
     return c;
 }
 
-// All-lane sum of a wave64 without LDS: pairs and quads by DPP quad_perm,
-// quads of a 16-lane row by DPP row_ror 12 / 8 (lane 0 of each row then holds
-// the row sum), the four rows combined as (r0+r1)+(r2+r3) by row swaps.  Lane 0
-// holds the result (other lanes may differ in rounding; callers use lane 0).
-#define SLAM_DPP_D(v, ctrl)                                                                            \
-    __longlong_as_double(                                                                              \
-        (static_cast<long long>(__builtin_amdgcn_update_dpp(                                           \
-             0, static_cast<int>(__double_as_longlong(v) >> 32), ctrl, 0xF, 0xF, false))                \
-         << 32) |                                                                                      \
-        static_cast<unsigned int>(__builtin_amdgcn_update_dpp(                                         \
-            0, static_cast<int>(__double_as_longlong(v) & 0xffffffff), ctrl, 0xF, 0xF, false)))
+// A double moved between lanes of a 16-lane row by DPP (both halves).
+template <int CTRL>
+__device__ __forceinline__ double dpp_row(double v) {
+    const long long b = __double_as_longlong(v);
+    const int lo = __builtin_amdgcn_update_dpp(0, static_cast<int>(b & 0xffffffff), CTRL, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, static_cast<int>(b >> 32), CTRL, 0xF, 0xF, false);
+    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
+}
+
 // Lane `lane`'s double (lane wave-uniform) through SGPRs.
 __device__ __forceinline__ double readlane_d(double v, int lane) {
     const long long b = __double_as_longlong(v);
@@ -105,11 +103,16 @@ __device__ __forceinline__ double readlane_d(double v, int lane) {
     const int hi = __builtin_amdgcn_readlane(static_cast<int>(b >> 32), lane);
     return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
 }
+
+// All-lane sum of a wave64 without LDS: pairs and quads by DPP quad_perm,
+// quads of a 16-lane row by DPP row_ror 12 / 8 (lane 0 of each row then holds
+// the row sum), the four rows combined as (r0+r1)+(r2+r3) by row swaps.  Lane 0
+// holds the result (other lanes may differ in rounding; callers use lane 0).
 __device__ __forceinline__ double wave_sum(double v) {
-    v += SLAM_DPP_D(v, 0xB1);    // xor 1
-    v += SLAM_DPP_D(v, 0x4E);    // xor 2
-    v += SLAM_DPP_D(v, 0x12C);   // row_ror 12
-    v += SLAM_DPP_D(v, 0x128);   // row_ror 8
+    v += dpp_row<0xB1>(v);    // xor 1
+    v += dpp_row<0x4E>(v);    // xor 2
+    v += dpp_row<0x12C>(v);   // row_ror 12
+    v += dpp_row<0x128>(v);   // row_ror 8
     // rows: (r0 + r1) in rows 0-1, (r2 + r3) in rows 2-3 (gfx950 v_permlane16_swap),
     // then the halves (v_permlane32_swap): lane 0 holds (r0 + r1) + (r2 + r3)
     const long long b = __double_as_longlong(v);
@@ -125,7 +128,6 @@ __device__ __forceinline__ double wave_sum(double v) {
     return __longlong_as_double((static_cast<long long>(hi2[0]) << 32) | lo2[0]) +
            __longlong_as_double((static_cast<long long>(hi2[1]) << 32) | lo2[1]);
 }
-#undef SLAM_DPP_D
 
 // Deterministic block all-reduce of NV doubles; `red` is LDS scratch of
 // WAVES * NV doubles.  Every thread returns identical bits (fixed wave order).
@@ -218,18 +220,10 @@ __device__ __forceinline__ void swap16_d(double& a, double& b) {
 
 // Sum over the 16 lanes of each row; every lane of the row gets it.
 __device__ __forceinline__ double row_sum_d(double v) {
-#define SLAM_DPP_D(v, ctrl)                                                                            \
-    __longlong_as_double(                                                                              \
-        (static_cast<long long>(__builtin_amdgcn_update_dpp(                                           \
-             0, static_cast<int>(__double_as_longlong(v) >> 32), ctrl, 0xF, 0xF, false))                \
-         << 32) |                                                                                      \
-        static_cast<unsigned int>(__builtin_amdgcn_update_dpp(                                         \
-            0, static_cast<int>(__double_as_longlong(v) & 0xffffffff), ctrl, 0xF, 0xF, false)))
-    v += SLAM_DPP_D(v, 0xB1);    // xor 1
-    v += SLAM_DPP_D(v, 0x4E);    // xor 2
-    v += SLAM_DPP_D(v, 0x12C);   // row_ror 12
-    v += SLAM_DPP_D(v, 0x128);   // row_ror 8
-#undef SLAM_DPP_D
+    v += dpp_row<0xB1>(v);    // xor 1
+    v += dpp_row<0x4E>(v);    // xor 2
+    v += dpp_row<0x12C>(v);   // row_ror 12
+    v += dpp_row<0x128>(v);   // row_ror 8
     return v;
 }
 
@@ -303,6 +297,10 @@ __device__ __forceinline__ int f2ord(float f) {
 }
 __device__ __forceinline__ float ord2f(int o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
 
+// An int moved between lanes by DPP (bound_ctrl: an invalid source lane reads 0): the step of the integer
+// reductions here and of wave_reduce_i (icp_kernels.hip).
+#define SLAM_DPPI(v, ctrl) __builtin_amdgcn_mov_dpp((v), (ctrl), 0xF, 0xF, true)
+
 // Signed maxima of 8 per-lane values over the wave's 64 lanes in ONE
 // reduce-scatter (the integer form of wave_sum_exact16; max is exact, so the
 // order is free): v_permlane32_swap on pairs (8 -> 4 registers: lanes 0-31
@@ -324,7 +322,6 @@ __device__ __forceinline__ void wave_max8_i32(int (&v)[8]) {
         v[i] = max(static_cast<int>(p[0]), static_cast<int>(p[1]));
     }
     int x0 = v[0], x1 = v[1];
-#define SLAM_DPPI(v, ctrl) __builtin_amdgcn_mov_dpp((v), (ctrl), 0xF, 0xF, true)
     x0 = max(x0, SLAM_DPPI(x0, 0xB1));    // quad_perm [1,0,3,2]
     x1 = max(x1, SLAM_DPPI(x1, 0xB1));
     x0 = max(x0, SLAM_DPPI(x0, 0x4E));    // quad_perm [2,3,0,1]
@@ -333,7 +330,6 @@ __device__ __forceinline__ void wave_max8_i32(int (&v)[8]) {
     x1 = max(x1, SLAM_DPPI(x1, 0x124));
     x0 = max(x0, SLAM_DPPI(x0, 0x128));   // row_ror:8
     x1 = max(x1, SLAM_DPPI(x1, 0x128));
-#undef SLAM_DPPI
     v[0] = __builtin_amdgcn_readlane(x0, 0);
     v[2] = __builtin_amdgcn_readlane(x0, 16);
     v[1] = __builtin_amdgcn_readlane(x0, 32);

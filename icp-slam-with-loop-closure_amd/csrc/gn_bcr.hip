@@ -447,15 +447,6 @@ __global__ __launch_bounds__(kBcrThreads) void bcr_top_reg_kernel(double* __rest
     }
 }
 
-// A double moved between lanes of a 16-lane row by DPP (both halves).
-template <int CTRL>
-__device__ __forceinline__ double dpp_row(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, static_cast<int>(b & 0xffffffff), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, static_cast<int>(b >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
-}
-
 // Back-substitution of the odd blocks of level s: v = z - X x_p - Y x_n
 // (x_p / x_n staged in LDS, X / Y read in 128 B row segments, DPP row sums),
 // then x_i = C_i^-T v as the mat-vec (C_i^-1)^T v over the whole workgroup:

@@ -819,15 +819,6 @@ __global__ __launch_bounds__(kThreads) void back_schur_kernel(const double* __re
                                                              const double* __restrict__ xb, int32_t nbd, int32_t nb,
                                                              int32_t s, int32_t mc);
 
-// A double moved between lanes of a 16-lane row by DPP (both halves).
-template <int CTRL>
-__device__ __forceinline__ double dpp_row(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, static_cast<int>(b & 0xffffffff), CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, static_cast<int>(b >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
-}
-
 // Back-substitution of the odd blocks of level s: x_i = z_i - X_i x_p - Y_i x_n
 // (16 x 16 threads: thread (tr, tc) sums columns tc + 16 w of rows tr + 16 u from
 // 128 B row segments; DPP row sums).

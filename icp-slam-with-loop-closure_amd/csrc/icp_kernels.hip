@@ -273,8 +273,7 @@ __device__ __forceinline__ void trace_mark(const IcpArgs& a, int b, int what) {
 // order as their unsigned bits.  An integer min takes the DPP operand directly
 // (v_min_i32_dpp, bound_ctrl: one instruction per step), where fminf would
 // canonicalise both operands first (IEEE mode) behind a separate DPP move.
-// (f2ord / ord2f: common.hpp)
-#define SLAM_DPPI(v, ctrl) __builtin_amdgcn_mov_dpp((v), (ctrl), 0xF, 0xF, true)
+// (f2ord / ord2f, SLAM_DPPI: common.hpp)
 template <typename I, typename Op>
 __device__ __forceinline__ I wave_reduce_i(I v, Op op) {
     v = op(v, static_cast<I>(SLAM_DPPI(static_cast<int>(v), 0xB1)));    // quad_perm [1,0,3,2]
@@ -286,7 +285,6 @@ __device__ __forceinline__ I wave_reduce_i(I v, Op op) {
     const auto q = __builtin_amdgcn_permlane32_swap(static_cast<uint32_t>(v), static_cast<uint32_t>(v), false, false);
     return op(static_cast<I>(q[0]), static_cast<I>(q[1]));
 }
-#undef SLAM_DPPI
 struct MinI { __device__ int operator()(int a, int b) const { return min(a, b); } };
 struct MaxI { __device__ int operator()(int a, int b) const { return max(a, b); } };
 struct MinU { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return min(a, b); } };
@@ -952,6 +950,210 @@ __device__ __forceinline__ PairSetup stage_pair(const IcpArgs& a, int n1, int n2
     return r;
 }
 
+// ---------------------------------------------------------------------------
+// The parts of an ICP iteration that must round and behave the same in every
+// kernel family (icp_kernel, icp_team_kernel, icp_wide_kernel): written once,
+// used by all three.  The slot -> pair mapping, the
+// search and the way the sums travel between waves and workgroups stay with
+// each kernel.
+// ---------------------------------------------------------------------------
+
+// Per-pair prologue, before the staging.  The bounds test itself stays in each
+// kernel (its limits differ, and the compiler takes the ranges of n1 and n2 in
+// everything below from that branch: inside a helper they were lost, DESIGN.md
+// section 3.1b).
+// Resumed phase: out_iters holds -(iterations done) for a paused pair and the
+// final count for a finished one.  False: nothing left to do, the whole
+// workgroup leaves (uniform).
+__device__ __forceinline__ bool pair_resume(const IcpArgs& a, int b, int& it0) {
+    it0 = 0;
+    if (a.resume) {
+        const int s = a.out_iters[b];
+        if (s > 0 || s == kBadBounds) return false;
+        it0 = -s;
+    }
+    return true;
+}
+// The pair's scans: pc1 (n1 query points at p1) and pc2 (n2 candidates at p2).
+struct PairScans {
+    int n1, n2;
+    const double2* p1;
+    const double2* p2;
+};
+__device__ __forceinline__ PairScans pair_scans(const IcpArgs& a, int b) {
+    const int s1 = a.src_scan[b];
+    const int s2 = a.dst_scan[b];
+    const int64_t o1 = a.scan_off[s1];
+    const int64_t o2 = a.scan_off[s2];
+    PairScans s;
+    s.n1 = static_cast<int>(a.scan_off[s1 + 1] - o1);
+    s.n2 = static_cast<int>(a.scan_off[s2 + 1] - o2);
+    s.p1 = a.pts + o1;
+    s.p2 = a.pts + o2;
+    return s;
+}
+// The caller's bounds (max_n1 / max_n2) chose the instance and the LDS size: a
+// pair outside them would be computed wrongly, so its writing thread flags it
+// instead (slam_icp_status returns SLAM_EINVAL) and it is left undone.
+// (A single-step launch has no out_iters.)
+__device__ __forceinline__ void pair_out_of_bounds(const IcpArgs& a, int b, bool step) {
+    if (!step) a.out_iters[b] = kBadBounds;
+    a.out_err[b] = __builtin_nan("");
+    atomicOr(&g_icp_status, 1);
+}
+
+// After the staging: a resumed pair continues from its saved
+// state, the transform and the previous error (the ICP loop carries nothing
+// else that affects results); a new one starts from `init` and records it as
+// the history's row 0.
+struct PairState {
+    SE2 T;
+    double* hist;   // the pair's history rows (NULL: not recorded)
+    double last_err;
+};
+__device__ __forceinline__ PairState pair_state(const IcpArgs& a, int b, int it0, bool writer, bool with_hist) {
+    PairState s;
+    s.T = load_se2((it0 > 0 ? a.out_tf : a.init) + 9 * static_cast<int64_t>(b));
+    if (a.rotation_only) {   // src/icp.py:60-61 zeroes previous_transform[:2, 2]
+        s.T.m02 = 0.0;
+        s.T.m12 = 0.0;
+    }
+    s.hist = (with_hist && a.hist_stride > 0) ? a.out_hist + static_cast<int64_t>(b) * a.hist_stride * 9 : nullptr;
+    if (s.hist && writer && it0 == 0) store_se2(s.hist, s.T);
+    s.last_err = it0 > 0 ? a.out_err[b] : 0.0;
+    return s;
+}
+
+// The grids of an iteration's order-free sums (rsum_add): gm for the matched
+// pc2 coordinates and gs for the (p - c) m^T terms are per-pair constants
+// (stage_pair), gd for the squared distances follows from this iteration's
+// bound on the transformed queries, |q| <= (max row sum of |R|) pmax + max |t|.
+struct SumGrids {
+    double2 c;   // pc1[0], the cross-covariance centre
+    RsumGrid gm, gs, gd;
+};
+__device__ __forceinline__ SumGrids sum_grids(const SE2& T, const double* pconst, int n1) {
+    SumGrids g;
+    g.c = *reinterpret_cast<const double2*>(pconst + kPcX);
+    const double2 gmv = *reinterpret_cast<const double2*>(pconst + kGm1);
+    const double2 gsv = *reinterpret_cast<const double2*>(pconst + kGs1);
+    const double2 pcm = *reinterpret_cast<const double2*>(pconst + kPmax);   // (pmax, cmax)
+    const double bq = (fmax(fabs(T.m00) + fabs(T.m01), fabs(T.m10) + fabs(T.m11)) * pcm.x +
+                       fmax(fabs(T.m02), fabs(T.m12))) * (1.0 + 1e-12);   // >= |q|
+    g.gm = RsumGrid{gmv.x, gmv.y};
+    g.gs = RsumGrid{gsv.x, gsv.y};
+    g.gd = rsum_grid(2.0 * (bq + pcm.y) * (bq + pcm.y) * (1.0 + 1e-12), n1);
+    return g;
+}
+
+// One matched query's seven terms: m the matched pc2 point, d2 the exact
+// squared distance |T p - m|^2 (reference rounding: exact_d2 on the query), p
+// the untransformed pc1 point.
+__device__ __forceinline__ void sums_add(double (&acc)[16], const double2& m, double d2, const double2& p,
+                                         const SumGrids& g) {
+    rsum_add(m.x, g.gm, acc[0], acc[1]);
+    rsum_add(m.y, g.gm, acc[2], acc[3]);
+    rsum_add(d2, g.gd, acc[4], acc[5]);   // (pc1_t - pc2[corr])**2
+    const double ax = p.x - g.c.x, ay = p.y - g.c.y;
+    rsum_add(ax * m.x, g.gs, acc[6], acc[7]);
+    rsum_add(ax * m.y, g.gs, acc[8], acc[9]);
+    rsum_add(ay * m.x, g.gs, acc[10], acc[11]);
+    rsum_add(ay * m.y, g.gs, acc[12], acc[13]);
+}
+
+// src/icp.py:22-46 + 64-67 from the 16 exact sums (lane q holds value q, every
+// lane the same T): pc2_avg, pc1_avg = T mu_p, X Y^T = R_T [sum (p - c) m^T -
+// dp pc2_avg^T], the closed-form rotation, the translation, and Tn = D T.
+struct KabschOut {
+    SE2 Tn;
+    double err;
+};
+__device__ __forceinline__ KabschOut kabsch_from_sums(double tot, const SE2& T, const double* pconst, int n1,
+                                                      bool rotation_only) {
+    const double n = static_cast<double>(n1);
+    const double mvx = (readlane_d(tot, 0) + readlane_d(tot, 1)) / n;   // pc2_avg
+    const double mvy = (readlane_d(tot, 2) + readlane_d(tot, 3)) / n;
+    KabschOut o;
+    o.err = readlane_d(tot, 4) + readlane_d(tot, 5);
+    const double2 dp = *reinterpret_cast<const double2*>(pconst + kDpX);
+    const double2 mup = *reinterpret_cast<const double2*>(pconst + kMupX);
+    const double mux = fma(T.m02, 1.0, fma(T.m01, mup.y, T.m00 * mup.x));   // pc1_avg = T mu_p
+    const double muy = fma(T.m12, 1.0, fma(T.m11, mup.y, T.m10 * mup.x));
+    // S_p = sum (p - mu_p)(m - pc2_avg)^T, then S = X @ Y.T = R_T S_p
+    const double p00 = fma(-dp.x, mvx, readlane_d(tot, 6) + readlane_d(tot, 7));
+    const double p01 = fma(-dp.x, mvy, readlane_d(tot, 8) + readlane_d(tot, 9));
+    const double p10 = fma(-dp.y, mvx, readlane_d(tot, 10) + readlane_d(tot, 11));
+    const double p11 = fma(-dp.y, mvy, readlane_d(tot, 12) + readlane_d(tot, 13));
+    double s[4];
+    s[0] = fma(T.m01, p10, T.m00 * p00);
+    s[1] = fma(T.m01, p11, T.m00 * p01);
+    s[2] = fma(T.m11, p10, T.m10 * p00);
+    s[3] = fma(T.m11, p11, T.m10 * p01);
+
+    // ---- closed-form 2x2 Kabsch: R maximising tr(R S) ---------------------
+    // Equals V diag(1, det(V U^T)) U^T of the reference's SVD route.
+    const double cs = s[0] + s[3];
+    const double sn = s[1] - s[2];
+    const double r = sqrt(cs * cs + sn * sn);
+    const double c = r > 0.0 ? cs / r : 1.0;
+    const double si = r > 0.0 ? sn / r : 0.0;
+    // t = pc2_avg - R @ pc1_avg (dgemv order)
+    double tx = mvx - fma(-si, muy, c * mux);
+    double ty = mvy - fma(c, muy, si * mux);
+    if (rotation_only) {   // src/icp.py:65-66
+        tx = 0.0;
+        ty = 0.0;
+    }
+    SE2 D;
+    D.m00 = c;  D.m01 = -si; D.m02 = tx;
+    D.m10 = si; D.m11 = c;   D.m12 = ty;
+    o.Tn = se2_mul(D, T);   // src/icp.py:67
+    return o;
+}
+
+// PRUNE searches: the motion of the next iteration's queries, (Tn - T) p in
+// fp32; dsig bounds its evaluation error (4u of |dT||p|) and the fp64 rounding
+// of both transforms (|R| <= 1 + 1e-9, |p| <= pmax).  Wave-uniform (SGPRs).
+__device__ __forceinline__ void next_motion(const SE2& T, const SE2& Tn, float pmax, float (&dT)[6], float& dsig) {
+    dT[0] = uniform_f(static_cast<float>(Tn.m00 - T.m00));
+    dT[1] = uniform_f(static_cast<float>(Tn.m01 - T.m01));
+    dT[2] = uniform_f(static_cast<float>(Tn.m02 - T.m02));
+    dT[3] = uniform_f(static_cast<float>(Tn.m10 - T.m10));
+    dT[4] = uniform_f(static_cast<float>(Tn.m11 - T.m11));
+    dT[5] = uniform_f(static_cast<float>(Tn.m12 - T.m12));
+    const float rr = fmaxf(fabsf(dT[0]) + fabsf(dT[1]), fabsf(dT[3]) + fabsf(dT[4]));
+    const float tt = fmaxf(fabsf(dT[2]), fabsf(dT[5]));
+    const float big = static_cast<float>(fabs(T.m02) + fabs(T.m12) + fabs(Tn.m02) + fabs(Tn.m12));
+    dsig = uniform_f(1e-6f * (rr * pmax + tt) + 1e-9f * (pmax + big) + 1e-30f);
+}
+
+// The pair's outputs when it stops (out_iters = iterations run) or pauses at a
+// scheduler phase boundary (out_iters = -(iterations run); the last error
+// change orders the survivors for the next phase).  Called by the pair's one
+// writing thread.  TRACE: the diagnostics' end mark; DRAIN: the launch's
+// stopped-pair count (IcpArgs::drain, when the launch has one).
+template <bool TRACE, bool DRAIN>
+__device__ __forceinline__ void pair_finished(const IcpArgs& a, int b, const SE2& Tn, double err, int it) {
+    store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
+    a.out_err[b] = err;
+    a.out_iters[b] = it + 1;
+    if constexpr (TRACE) trace_mark(a, b, 1);
+    if constexpr (DRAIN) {
+        if (a.drain) atomicAdd(a.drain, 1u);
+    }
+}
+template <bool TRACE, bool DRAIN>
+__device__ __forceinline__ void pair_paused(const IcpArgs& a, int b, const SE2& Tn, double err, int it, double derr) {
+    store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
+    a.out_err[b] = err;
+    a.out_iters[b] = -(it + 1);
+    a.sched_key[b] = static_cast<float>(derr);
+    if constexpr (TRACE) trace_mark(a, b, 1);
+    if constexpr (DRAIN) {
+        if (a.drain) atomicAdd(a.drain, 1u);
+    }
+}
+
 // DIAG: a diagnostics build of the kernel (per-phase s_memtime stamps of
 // workgroup 0, in-kernel candidate-evaluation counter); the product kernels
 // are compiled without any of it.
@@ -1006,32 +1208,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     //   = k * qstride + tid + gshift   (qstride = BLOCK, gshift = 0 without gangs)
     const int qstride = GANG ? BLOCK * parts : BLOCK;
     const int gshift = GANG ? (wave * (parts - 1) + part) * 64 : 0;   // wave-uniform
-    // resumed phase: out_iters holds -(iterations done) for a paused pair and
-    // the final count for a finished one (nothing left to do)
-    int it0 = 0;
-    if (a.resume) {
-        const int s = a.out_iters[b];
-        if (s > 0 || s == kBadBounds) return;   // uniform: the whole workgroup leaves
-        it0 = -s;
-    }
-    const int s1 = a.src_scan[b];
-    const int s2 = a.dst_scan[b];
-    const int64_t o1 = a.scan_off[s1];
-    const int64_t o2 = a.scan_off[s2];
-    const int n1 = static_cast<int>(a.scan_off[s1 + 1] - o1);
-    const int n2 = static_cast<int>(a.scan_off[s2 + 1] - o2);
-    const double2* __restrict__ p1 = a.pts + o1;
-    const double2* __restrict__ p2 = a.pts + o2;
+    int it0;
+    if (!pair_resume(a, b, it0)) return;   // uniform: the whole workgroup leaves
+    const PairScans sc = pair_scans(a, b);
+    const int n1 = sc.n1, n2 = sc.n2;
+    const double2* __restrict__ p1 = sc.p1;
+    const double2* __restrict__ p2 = sc.p2;
     const bool resident = n2 <= cap;
-    // the caller's bounds (max_n1 / max_n2) chose this instance and the LDS
-    // size: a pair outside them would be computed wrongly, so it is flagged
-    // instead (slam_icp_status returns SLAM_EINVAL) and left undone
     if (n1 < 1 || n2 < 1 || n1 > qstride * QPT || (SCREEN && !resident)) {
-        if (tid == 0 && part == 0) {
-            if (!STEP) a.out_iters[b] = kBadBounds;
-            a.out_err[b] = __builtin_nan("");
-            atomicOr(&g_icp_status, 1);
-        }
+        if (tid == 0 && part == 0) pair_out_of_bounds(a, b, STEP);
         return;   // uniform
     }
 
@@ -1077,18 +1262,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     }
     const int n2_pad = (n2 + kChunk - 1) / kChunk * kChunk;
 
-    // a resumed pair continues from its saved state: the transform and the
-    // previous error (the ICP loop carries nothing else that affects results)
-    SE2 T = load_se2((it0 > 0 ? a.out_tf : a.init) + 9 * static_cast<int64_t>(b));
-    if (a.rotation_only) {   // src/icp.py:60-61 zeroes previous_transform[:2, 2]
-        T.m02 = 0.0;
-        T.m12 = 0.0;
-    }
-    double* hist = (!STEP && a.hist_stride > 0)
-                       ? a.out_hist + static_cast<int64_t>(b) * a.hist_stride * 9
-                       : nullptr;
-    if (hist && tid == 0 && part == 0 && it0 == 0) store_se2(hist, T);
-    double last_err = it0 > 0 ? a.out_err[b] : 0.0;
+    PairState st0 = pair_state(a, b, it0, tid == 0 && part == 0, !STEP);
+    SE2& T = st0.T;   // the loop's state, updated in place
+    double* const hist = st0.hist;
+    double& last_err = st0.last_err;
     __syncthreads();
 
     unsigned long long tph[5] = {0, 0, 0, 0, 0}, tprev = 0, tsub[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1360,14 +1537,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             // search (dq), so the query point need not stay live or be recomputed
             int tr = threadIdx.x;
             asm volatile("" : "+v"(tr));
-            const double2 c = *reinterpret_cast<const double2*>(pconst + kPcX);
-            const double2 gmv = *reinterpret_cast<const double2*>(pconst + kGm1);
-            const double2 gsv = *reinterpret_cast<const double2*>(pconst + kGs1);
-            const double2 pcm = *reinterpret_cast<const double2*>(pconst + kPmax);   // (pmax, cmax)
-            const double bq = (fmax(fabs(T.m00) + fabs(T.m01), fabs(T.m10) + fabs(T.m11)) * pcm.x +
-                               fmax(fabs(T.m02), fabs(T.m12))) * (1.0 + 1e-12);   // >= |q|
-            const RsumGrid gm{gmv.x, gmv.y}, gs{gsv.x, gsv.y};
-            const RsumGrid gd = rsum_grid(2.0 * (bq + pcm.y) * (bq + pcm.y) * (1.0 + 1e-12), n1);
+            const SumGrids sg = sum_grids(T, pconst, n1);
             double acc[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = 0.0;
@@ -1377,14 +1547,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 if (i < n1) {
                     const double2 m = resident ? cand[bi[k]] : p2[bi[k]];
                     const double2 p = p1[i];
-                    rsum_add(m.x, gm, acc[0], acc[1]);
-                    rsum_add(m.y, gm, acc[2], acc[3]);
-                    rsum_add(dq[k], gd, acc[4], acc[5]);   // (pc1_t - pc2[corr])**2
-                    const double ax = p.x - c.x, ay = p.y - c.y;
-                    rsum_add(ax * m.x, gs, acc[6], acc[7]);
-                    rsum_add(ax * m.y, gs, acc[8], acc[9]);
-                    rsum_add(ay * m.x, gs, acc[10], acc[11]);
-                    rsum_add(ay * m.y, gs, acc[12], acc[13]);
+                    sums_add(acc, m, dq[k], p, sg);
                 }
             }
             tot = block_sum_exact16<WAVES>(acc, ((it - it0) & 1) ? red0 : red1);
@@ -1408,6 +1571,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 #else
         {
 #endif
+            // The TWIN of kabsch_from_sums, expression for expression: change both
+            // together.  Written out here because through the helper this kernel's
+            // 10k-pair batch ran 0.7 % slower (3.975 against 3.949 ms: wave 0's
+            // serial stretch between two barriers).
             const double n = static_cast<double>(n1);
             const double mvx = (readlane_d(tot, 0) + readlane_d(tot, 1)) / n;   // pc2_avg
             const double mvy = (readlane_d(tot, 2) + readlane_d(tot, 3)) / n;
@@ -1416,7 +1583,6 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             const double2 mup = *reinterpret_cast<const double2*>(pconst + kMupX);
             const double mux = fma(T.m02, 1.0, fma(T.m01, mup.y, T.m00 * mup.x));   // pc1_avg = T mu_p
             const double muy = fma(T.m12, 1.0, fma(T.m11, mup.y, T.m10 * mup.x));
-            // S_p = sum (p - mu_p)(m - pc2_avg)^T, then S = X @ Y.T = R_T S_p
             const double p00 = fma(-dp.x, mvx, readlane_d(tot, 6) + readlane_d(tot, 7));
             const double p01 = fma(-dp.x, mvy, readlane_d(tot, 8) + readlane_d(tot, 9));
             const double p10 = fma(-dp.y, mvx, readlane_d(tot, 10) + readlane_d(tot, 11));
@@ -1426,15 +1592,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             s[1] = fma(T.m01, p11, T.m00 * p01);
             s[2] = fma(T.m11, p10, T.m10 * p00);
             s[3] = fma(T.m11, p11, T.m10 * p01);
-
-            // ---- closed-form 2x2 Kabsch: R maximising tr(R S) ---------------------
-            // Equals V diag(1, det(V U^T)) U^T of the reference's SVD route.
             const double cs = s[0] + s[3];
             const double sn = s[1] - s[2];
             const double r = sqrt(cs * cs + sn * sn);
             const double c = r > 0.0 ? cs / r : 1.0;
             const double si = r > 0.0 ? sn / r : 0.0;
-            // t = pc2_avg - R @ pc1_avg (dgemv order)
             double tx = mvx - fma(-si, muy, c * mux);
             double ty = mvy - fma(c, muy, si * mux);
             if (a.rotation_only) {   // src/icp.py:65-66
@@ -1495,34 +1657,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             const bool stop = (err < a.epsilon) || (it > a.max_iters) ||
                               (it > 0 && derr < a.stopping_thresh);
             last_err = err;
-            if constexpr (PRUNE) {
-                // motion of the next iteration's queries: (Tn - T) p, fp32; dsig bounds
-                // its evaluation error (4u of |dT||p|) and the fp64 rounding of both
-                // transforms (|R| <= 1 + 1e-9, |p| <= pmax)
-                dT[0] = uniform_f(static_cast<float>(Tn.m00 - T.m00));
-                dT[1] = uniform_f(static_cast<float>(Tn.m01 - T.m01));
-                dT[2] = uniform_f(static_cast<float>(Tn.m02 - T.m02));
-                dT[3] = uniform_f(static_cast<float>(Tn.m10 - T.m10));
-                dT[4] = uniform_f(static_cast<float>(Tn.m11 - T.m11));
-                dT[5] = uniform_f(static_cast<float>(Tn.m12 - T.m12));
-                const float rr = fmaxf(fabsf(dT[0]) + fabsf(dT[1]), fabsf(dT[3]) + fabsf(dT[4]));
-                const float tt = fmaxf(fabsf(dT[2]), fabsf(dT[5]));
-                const float big = static_cast<float>(fabs(T.m02) + fabs(T.m12) + fabs(Tn.m02) + fabs(Tn.m12));
-                dsig = uniform_f(1e-6f * (rr * pmax + tt) + 1e-9f * (pmax + big) + 1e-30f);
-            }
+            if constexpr (PRUNE) next_motion(T, Tn, pmax, dT, dsig);
             // Tn is identical in every lane: keep it in SGPRs
             T.m00 = uniform_d(Tn.m00); T.m01 = uniform_d(Tn.m01); T.m02 = uniform_d(Tn.m02);
             T.m10 = uniform_d(Tn.m10); T.m11 = uniform_d(Tn.m11); T.m12 = uniform_d(Tn.m12);
             if (stop) {
                 flush_stamps();
                 if (counting && lane == 0) atomicAdd(a.evals, nev);
-                if (tid == 0 && part == 0) {
-                    store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
-                    a.out_err[b] = err;
-                    a.out_iters[b] = it + 1;
-                    trace_mark(a, b, 1);
-                    if (!GANG && a.drain) atomicAdd(a.drain, 1u);
-                }
+                if (tid == 0 && part == 0) pair_finished<true, !GANG>(a, b, Tn, err, it);
                 return;
             }
             if ((a.phase_cap > 0 && it + 1 - it0 >= a.phase_cap) || drain_now) {
@@ -1547,14 +1689,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                         }
                     }
                 }
-                if (tid == 0 && part == 0) {
-                    store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
-                    a.out_err[b] = err;
-                    a.out_iters[b] = -(it + 1);
-                    a.sched_key[b] = static_cast<float>(derr);
-                    trace_mark(a, b, 1);
-                    if (!GANG && a.drain) atomicAdd(a.drain, 1u);
-                }
+                if (tid == 0 && part == 0) pair_paused<true, !GANG>(a, b, Tn, err, it, derr);
                 return;
             }
         }
@@ -1617,40 +1752,24 @@ __global__ __launch_bounds__(kTeamBlock) void icp_team_kernel(IcpArgs a) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int it0 = 0;
-    if (a.resume) {
-        const int s = a.out_iters[b];
-        if (s > 0 || s == kBadBounds) return;
-        it0 = -s;
-    }
-    const int s1 = a.src_scan[b];
-    const int s2 = a.dst_scan[b];
-    const int64_t o1 = a.scan_off[s1];
-    const int64_t o2 = a.scan_off[s2];
-    const int n1 = static_cast<int>(a.scan_off[s1 + 1] - o1);
-    const int n2 = static_cast<int>(a.scan_off[s2 + 1] - o2);
-    const double2* __restrict__ p1 = a.pts + o1;
-    const double2* __restrict__ p2 = a.pts + o2;
+    int it0;
+    if (!pair_resume(a, b, it0)) return;   // uniform
+    const PairScans sc = pair_scans(a, b);
+    const int n1 = sc.n1, n2 = sc.n2;
+    const double2* __restrict__ p1 = sc.p1;
+    const double2* __restrict__ p2 = sc.p2;
     if (n1 < 1 || n2 < 1 || n1 > 64 * parts || n2 > cap) {
-        if (tid == 0 && part == 0) {
-            a.out_iters[b] = kBadBounds;
-            a.out_err[b] = __builtin_nan("");
-            atomicOr(&g_icp_status, 1);
-        }
+        if (tid == 0 && part == 0) pair_out_of_bounds(a, b, false);
         return;
     }
     const PairSetup ps = stage_pair<kTeamBlock, true, true>(a, n1, n2, p1, p2, true, cand, candf, box8, red0, red1,
                                                             pconst);
     const int nsub = ps.nsub;
     const bool screen = ps.screen;
-    SE2 T = load_se2((it0 > 0 ? a.out_tf : a.init) + 9 * static_cast<int64_t>(b));
-    if (a.rotation_only) {
-        T.m02 = 0.0;
-        T.m12 = 0.0;
-    }
-    double* hist = a.hist_stride > 0 ? a.out_hist + static_cast<int64_t>(b) * a.hist_stride * 9 : nullptr;
-    if (hist && tid == 0 && part == 0 && it0 == 0) store_se2(hist, T);
-    double last_err = it0 > 0 ? a.out_err[b] : 0.0;
+    const PairState st0 = pair_state(a, b, it0, tid == 0 && part == 0, true);
+    SE2 T = st0.T;
+    double* hist = st0.hist;
+    double last_err = st0.last_err;
     float dT[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dsig = 0.0f;
     int prev = -1;      // last match (identical in every wave)
     uint32_t st = 0;    // clearance word (radius | window start), see st_pack
@@ -1880,27 +1999,13 @@ __global__ __launch_bounds__(kTeamBlock) void icp_team_kernel(IcpArgs a) {
         // sums: wave 0's 64 queries (the other waves hold the same ones)
         double tot;
         {
-            const double2 c = *reinterpret_cast<const double2*>(pconst + kPcX);
-            const double2 gmv = *reinterpret_cast<const double2*>(pconst + kGm1);
-            const double2 gsv = *reinterpret_cast<const double2*>(pconst + kGs1);
-            const double2 pcm = *reinterpret_cast<const double2*>(pconst + kPmax);
-            const double bq = (fmax(fabs(T.m00) + fabs(T.m01), fabs(T.m10) + fabs(T.m11)) * pcm.x +
-                               fmax(fabs(T.m02), fabs(T.m12))) * (1.0 + 1e-12);
-            const RsumGrid gm{gmv.x, gmv.y}, gs{gsv.x, gsv.y};
-            const RsumGrid gd = rsum_grid(2.0 * (bq + pcm.y) * (bq + pcm.y) * (1.0 + 1e-12), n1);
+            const SumGrids sg = sum_grids(T, pconst, n1);
             double acc[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = 0.0;
             if (wave == 0 && valid) {
                 const double2 m = cand[bi];
-                rsum_add(m.x, gm, acc[0], acc[1]);
-                rsum_add(m.y, gm, acc[2], acc[3]);
-                rsum_add(exact_d2(m.x, m.y, qx, qy), gd, acc[4], acc[5]);
-                const double ax = x - c.x, ay = y - c.y;
-                rsum_add(ax * m.x, gs, acc[6], acc[7]);
-                rsum_add(ax * m.y, gs, acc[8], acc[9]);
-                rsum_add(ay * m.x, gs, acc[10], acc[11]);
-                rsum_add(ay * m.y, gs, acc[12], acc[13]);
+                sums_add(acc, m, exact_d2(m.x, m.y, qx, qy), make_double2(x, y), sg);
             }
             tot = block_sum_exact16<WAVES>(acc, ((it - it0) & 1) ? red0 : red1);
             tstamp(7);
@@ -1912,73 +2017,25 @@ __global__ __launch_bounds__(kTeamBlock) void icp_team_kernel(IcpArgs a) {
             }
         }
         tstamp(8);
-        const double n = static_cast<double>(n1);
-        const double mvx = (readlane_d(tot, 0) + readlane_d(tot, 1)) / n;
-        const double mvy = (readlane_d(tot, 2) + readlane_d(tot, 3)) / n;
-        const double err = readlane_d(tot, 4) + readlane_d(tot, 5);
-        const double2 dp = *reinterpret_cast<const double2*>(pconst + kDpX);
-        const double2 mup = *reinterpret_cast<const double2*>(pconst + kMupX);
-        const double mux = fma(T.m02, 1.0, fma(T.m01, mup.y, T.m00 * mup.x));
-        const double muy = fma(T.m12, 1.0, fma(T.m11, mup.y, T.m10 * mup.x));
-        const double p00 = fma(-dp.x, mvx, readlane_d(tot, 6) + readlane_d(tot, 7));
-        const double p01 = fma(-dp.x, mvy, readlane_d(tot, 8) + readlane_d(tot, 9));
-        const double p10 = fma(-dp.y, mvx, readlane_d(tot, 10) + readlane_d(tot, 11));
-        const double p11 = fma(-dp.y, mvy, readlane_d(tot, 12) + readlane_d(tot, 13));
-        const double s00 = fma(T.m01, p10, T.m00 * p00);
-        const double s01 = fma(T.m01, p11, T.m00 * p01);
-        const double s10 = fma(T.m11, p10, T.m10 * p00);
-        const double s11 = fma(T.m11, p11, T.m10 * p01);
-        const double cs = s00 + s11;
-        const double sn = s01 - s10;
-        const double r = sqrt(cs * cs + sn * sn);
-        const double co = r > 0.0 ? cs / r : 1.0;
-        const double si = r > 0.0 ? sn / r : 0.0;
-        double tx = mvx - fma(-si, muy, co * mux);
-        double ty = mvy - fma(co, muy, si * mux);
-        if (a.rotation_only) {
-            tx = 0.0;
-            ty = 0.0;
-        }
-        SE2 D;
-        D.m00 = co; D.m01 = -si; D.m02 = tx;
-        D.m10 = si; D.m11 = co;  D.m12 = ty;
-        const SE2 Tn = se2_mul(D, T);
+        const KabschOut ko = kabsch_from_sums(tot, T, pconst, n1, a.rotation_only != 0);
+        const SE2& Tn = ko.Tn;
+        const double err = ko.err;
         if (hist && tid == 0 && part == 0) store_se2(hist + 9 * (it + 1), Tn);
         const double derr = fabs(last_err - err);
         const bool stop = (err < a.epsilon) || (it > a.max_iters) || (it > 0 && derr < a.stopping_thresh);
         last_err = err;
-        dT[0] = uniform_f(static_cast<float>(Tn.m00 - T.m00));
-        dT[1] = uniform_f(static_cast<float>(Tn.m01 - T.m01));
-        dT[2] = uniform_f(static_cast<float>(Tn.m02 - T.m02));
-        dT[3] = uniform_f(static_cast<float>(Tn.m10 - T.m10));
-        dT[4] = uniform_f(static_cast<float>(Tn.m11 - T.m11));
-        dT[5] = uniform_f(static_cast<float>(Tn.m12 - T.m12));
-        {
-            const float rr = fmaxf(fabsf(dT[0]) + fabsf(dT[1]), fabsf(dT[3]) + fabsf(dT[4]));
-            const float tt = fmaxf(fabsf(dT[2]), fabsf(dT[5]));
-            const float big = static_cast<float>(fabs(T.m02) + fabs(T.m12) + fabs(Tn.m02) + fabs(Tn.m12));
-            dsig = uniform_f(1e-6f * (rr * ps.pmax + tt) + 1e-9f * (ps.pmax + big) + 1e-30f);
-        }
+        next_motion(T, Tn, ps.pmax, dT, dsig);
         T.m00 = uniform_d(Tn.m00); T.m01 = uniform_d(Tn.m01); T.m02 = uniform_d(Tn.m02);
         T.m10 = uniform_d(Tn.m10); T.m11 = uniform_d(Tn.m11); T.m12 = uniform_d(Tn.m12);
         tstamp(9);
         if (stop) {
             tflush();
-            if (tid == 0 && part == 0) {
-                store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
-                a.out_err[b] = err;
-                a.out_iters[b] = it + 1;
-            }
+            if (tid == 0 && part == 0) pair_finished<false, false>(a, b, Tn, err, it);
             return;
         }
         if (a.phase_cap > 0 && it + 1 - it0 >= a.phase_cap) {
             tflush();
-            if (tid == 0 && part == 0) {
-                store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
-                a.out_err[b] = err;
-                a.out_iters[b] = -(it + 1);
-                a.sched_key[b] = static_cast<float>(derr);
-            }
+            if (tid == 0 && part == 0) pair_paused<false, false>(a, b, Tn, err, it, derr);
             return;
         }
     }
@@ -2025,49 +2082,6 @@ constexpr int kUWin = SLAM_WIDE_UWIN;
 // A wide slot's global slab (float4 units): the fp32 candidate pairs (cap / 2),
 // then one bounding box per chunk of kChunk candidates (cap / kChunk)
 __host__ __device__ constexpr int64_t wide_slab_f4(int cap) { return cap / 2 + cap / kChunk; }
-
-// src/icp.py:22-46 + 64-67 from the 16 exact partial sums (lane q holds value
-// q, every lane the same T): the Kabsch update of icp_kernel, one wave.
-struct KabschOut {
-    SE2 Tn;
-    double err;
-};
-__device__ __forceinline__ KabschOut kabsch_from_sums(double tot, const SE2& T, const double* pconst, int n1,
-                                                      bool rotation_only) {
-    const double n = static_cast<double>(n1);
-    const double mvx = (readlane_d(tot, 0) + readlane_d(tot, 1)) / n;   // pc2_avg
-    const double mvy = (readlane_d(tot, 2) + readlane_d(tot, 3)) / n;
-    KabschOut o;
-    o.err = readlane_d(tot, 4) + readlane_d(tot, 5);
-    const double2 dp = *reinterpret_cast<const double2*>(pconst + kDpX);
-    const double2 mup = *reinterpret_cast<const double2*>(pconst + kMupX);
-    const double mux = fma(T.m02, 1.0, fma(T.m01, mup.y, T.m00 * mup.x));   // pc1_avg = T mu_p
-    const double muy = fma(T.m12, 1.0, fma(T.m11, mup.y, T.m10 * mup.x));
-    const double p00 = fma(-dp.x, mvx, readlane_d(tot, 6) + readlane_d(tot, 7));
-    const double p01 = fma(-dp.x, mvy, readlane_d(tot, 8) + readlane_d(tot, 9));
-    const double p10 = fma(-dp.y, mvx, readlane_d(tot, 10) + readlane_d(tot, 11));
-    const double p11 = fma(-dp.y, mvy, readlane_d(tot, 12) + readlane_d(tot, 13));
-    const double s00 = fma(T.m01, p10, T.m00 * p00);
-    const double s01 = fma(T.m01, p11, T.m00 * p01);
-    const double s10 = fma(T.m11, p10, T.m10 * p00);
-    const double s11 = fma(T.m11, p11, T.m10 * p01);
-    const double cs = s00 + s11;
-    const double sn = s01 - s10;
-    const double r = sqrt(cs * cs + sn * sn);
-    const double co = r > 0.0 ? cs / r : 1.0;
-    const double si = r > 0.0 ? sn / r : 0.0;
-    double tx = mvx - fma(-si, muy, co * mux);
-    double ty = mvy - fma(co, muy, si * mux);
-    if (rotation_only) {
-        tx = 0.0;
-        ty = 0.0;
-    }
-    SE2 D;
-    D.m00 = co; D.m01 = -si; D.m02 = tx;
-    D.m10 = si; D.m11 = co;  D.m12 = ty;
-    o.Tn = se2_mul(D, T);
-    return o;
-}
 
 // The wide pairs' fp32 candidates in the pair layout of candf (cf_put), one
 // `cap` slab per wide slot, in global memory: the wide kernel streams them
@@ -2141,29 +2155,21 @@ __global__ __launch_bounds__(64 * kWideWaves * G) void icp_wide_kernel(IcpArgs a
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int gq = wave % G, wg = wave / G;   // query group in the workgroup, wave in the group
-    int it0 = 0;
-    if (a.resume) {
-        const int s = a.out_iters[b];
-        if (s > 0 || s == kBadBounds) return;
-        it0 = -s;
-    }
-    const int s1 = a.src_scan[b], s2 = a.dst_scan[b];
-    const int64_t o1 = a.scan_off[s1], o2 = a.scan_off[s2];
-    const int n1 = static_cast<int>(a.scan_off[s1 + 1] - o1);
-    const int n2 = static_cast<int>(a.scan_off[s2 + 1] - o2);
-    const double2* __restrict__ p1 = a.pts + o1;
-    const double2* __restrict__ p2 = a.pts + o2;
+    int it0;
+    if (!pair_resume(a, b, it0)) return;   // uniform
+    const PairScans sc = pair_scans(a, b);
+    const int n1 = sc.n1, n2 = sc.n2;
+    const double2* __restrict__ p1 = sc.p1;
+    const double2* __restrict__ p2 = sc.p2;
     if (n1 < 1 || n2 < 1 || n1 > 64 * G * parts || n2 > cap) {
-        if (tid == 0 && part == 0) {
-            a.out_iters[b] = kBadBounds;
-            a.out_err[b] = __builtin_nan("");
-            atomicOr(&g_icp_status, 1);
-        }
+        if (tid == 0 && part == 0) pair_out_of_bounds(a, b, false);
         return;
     }
     if (tid == 0 && part == 0) trace_mark(a, b, 0);
     const PairSetup ps = stage_pair<WBLK, true, false>(a, n1, n2, p1, p2, true, cand, candf, nullptr, red0, red1,
                                                        pconst);
+    // pair_state's body, written out: through the helper the 2,500- and
+    // 1,250-pair shards ran 0.5-0.8 % slower
     SE2 T = load_se2((it0 > 0 ? a.out_tf : a.init) + 9 * static_cast<int64_t>(b));
     if (a.rotation_only) {
         T.m02 = 0.0;
@@ -2345,28 +2351,11 @@ __global__ __launch_bounds__(64 * kWideWaves * G) void icp_wide_kernel(IcpArgs a
             tstamp(3);
             pm[gq * 64 + lane] = bi;   // the next iteration's prediction (read after the barriers below)
             // sums (as icp_kernel step 4), this group's 64 queries
-            const double2 c = *reinterpret_cast<const double2*>(pconst + kPcX);
-            const double2 gmv = *reinterpret_cast<const double2*>(pconst + kGm1);
-            const double2 gsv = *reinterpret_cast<const double2*>(pconst + kGs1);
-            const double2 pcm = *reinterpret_cast<const double2*>(pconst + kPmax);
-            const double bq = (fmax(fabs(T.m00) + fabs(T.m01), fabs(T.m10) + fabs(T.m11)) * pcm.x +
-                               fmax(fabs(T.m02), fabs(T.m12))) * (1.0 + 1e-12);
-            const RsumGrid gm{gmv.x, gmv.y}, gs{gsv.x, gsv.y};
-            const RsumGrid gd = rsum_grid(2.0 * (bq + pcm.y) * (bq + pcm.y) * (1.0 + 1e-12), n1);
+            const SumGrids sg = sum_grids(T, pconst, n1);
             double acc[16];
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = 0.0;
-            if (valid) {
-                const double2 m = cand[bi];
-                rsum_add(m.x, gm, acc[0], acc[1]);
-                rsum_add(m.y, gm, acc[2], acc[3]);
-                rsum_add(dq, gd, acc[4], acc[5]);
-                const double ax = x - c.x, ay = y - c.y;
-                rsum_add(ax * m.x, gs, acc[6], acc[7]);
-                rsum_add(ax * m.y, gs, acc[8], acc[9]);
-                rsum_add(ay * m.x, gs, acc[10], acc[11]);
-                rsum_add(ay * m.y, gs, acc[12], acc[13]);
-            }
+            if (valid) sums_add(acc, cand[bi], dq, make_double2(x, y), sg);
             tot = wave_sum_exact16(acc);
             if (G > 1 && gq == 1 && lane < 16) gsum[lane] = tot;
         }
@@ -2394,21 +2383,10 @@ __global__ __launch_bounds__(64 * kWideWaves * G) void icp_wide_kernel(IcpArgs a
                 last_err = err;
                 if (stop) {
                     flag = 1.0;
-                    if (lane == 0 && part == 0) {
-                        store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
-                        a.out_err[b] = err;
-                        a.out_iters[b] = it + 1;
-                        trace_mark(a, b, 1);
-                    }
+                    if (lane == 0 && part == 0) pair_finished<true, false>(a, b, Tn, err, it);
                 } else if (a.phase_cap > 0 && it + 1 - it0 >= a.phase_cap) {
                     flag = 2.0;
-                    if (lane == 0 && part == 0) {
-                        store_se2(a.out_tf + 9 * static_cast<int64_t>(b), Tn);
-                        a.out_err[b] = err;
-                        a.out_iters[b] = -(it + 1);
-                        a.sched_key[b] = static_cast<float>(derr);
-                        trace_mark(a, b, 1);
-                    }
+                    if (lane == 0 && part == 0) pair_paused<true, false>(a, b, Tn, err, it, derr);
                 }
                 if (lane == 0) {
                     tb[0] = Tn.m00; tb[1] = Tn.m01; tb[2] = Tn.m02;
@@ -3552,9 +3530,9 @@ int slam_icp_set_eval_counter(void* dev_u64) {
     g_icp_evals = reinterpret_cast<unsigned long long*>(dev_u64);
     return ok();
 }
-// Phased scheduling of large batches (see launch_batch): phase-1 iterations
-// (0 = one launch) and the smallest batch it applies to.  Results do not
-// depend on it (tests/test_icp_gpu.py::test_schedule_is_invisible).
+// Phase 2's CU-exclusive heads (g_sched_heads: the slowest-keyed pairs, at
+// most one per 16; 0: none) and gangs (g_sched_gangs pairs on `parts`
+// workgroups each; parts 0: teams).  Either selects the explicit settings.
 int slam_icp_set_schedule_heads(int heads) {
     if (heads < 0) return fail(SLAM_EINVAL, "schedule: negative head count");
     g_sched_heads = heads;
@@ -3569,9 +3547,6 @@ int slam_icp_set_schedule_gangs(int gangs, int parts) {
     g_sched_auto = 0;
     return ok();
 }
-// Gang parts that timed out waiting for a partner since the last call (their
-// pairs were re-run on single workgroups: results stay valid); read-and-clear.
-// Synchronises the device.
 // Wide tier: the `pairs` slowest-keyed pairs of a batch below 8,192 pairs on
 // icp_wide_kernel (before the gangs), workgroups requesting 1/share of a CU's
 // LDS (1: CU-exclusive).  Results are bit-identical.  0 = off.
@@ -3605,8 +3580,6 @@ int slam_icp_set_sched_sort_one(int on) {
     g_sched_sort_one = on ? 1 : 0;
     return ok();
 }
-// Diagnostics: batches of fewer than `pairs` pairs get the tail tiers (heads,
-// gangs, wide); 0 restores the default (4,096).
 // Diagnostics: the XCD-aware pair map of launches in stream order: runs of
 // `run` consecutive pairs per XCD (default 16; 0 = identity; -1 restores the
 // default).  Results do not depend on it.
@@ -3667,11 +3640,16 @@ int slam_icp_set_schedule_auto(int on) {
     }
     return ok();
 }
+// Diagnostics: batches of fewer than `pairs` pairs get the tail tiers (heads,
+// gangs, wide); 0 restores the default (4,096).
 int slam_icp_set_tier_limit(int pairs) {
     if (pairs < 0) return fail(SLAM_EINVAL, "tier limit %d < 0", pairs);
     g_tiers_below = pairs ? pairs : kHeadsMaxPairs;
     return ok();
 }
+// Gang parts that timed out waiting for a partner since the last call (their
+// pairs were re-run on single workgroups: results stay valid); read-and-clear.
+// Synchronises the device.
 int slam_icp_gang_timeouts(void) {
     int v = 0;
     const int zero = 0;
@@ -3681,9 +3659,9 @@ int slam_icp_gang_timeouts(void) {
         return fail(SLAM_EHIP, "gang timeouts: read");
     return v;
 }
-// Diagnostics: the longest wait of a gang exchange for its partners, in
-// s_memrealtime ticks (100 MHz); 0 restores the default (0.2 s).  Tiny values
-// force timeouts (the repair path).
+// Diagnostics: the longest wait of a launch's FIRST exchange of a pair, whose
+// partners may not be resident yet (kGangWaitFirstTicks), in s_memrealtime
+// ticks; 0 restores the default (4 ms).  Every later exchange: slam_icp_set_gang_wait.
 int slam_icp_set_gang_first_wait(uint32_t ticks) {
     g_gang_wait_first = ticks ? ticks : kGangWaitFirstTicks;
     return ok();
@@ -3713,6 +3691,9 @@ int slam_icp_diag_occupy(int workgroups, uint32_t ticks, void* stream) {
                        static_cast<unsigned long long*>(nullptr));
     return check_launch("occupy kernel");
 }
+// Diagnostics: the longest wait of a gang exchange for its partners, in
+// s_memrealtime ticks (100 MHz); 0 restores the default (0.2 s).  Tiny values
+// force timeouts (the repair path).
 int slam_icp_set_gang_wait(uint32_t ticks) {
     g_gang_wait = ticks ? ticks : kGangWaitTicks;
     return ok();
@@ -3751,6 +3732,9 @@ int slam_icp_set_drain(int pairs) {
     return ok();
 }
 
+// Phased scheduling of large batches (see launch_batch): phase-1 iterations
+// (0 = one launch, -1 = automatic) and the smallest batch it applies to.  Results
+// do not depend on it (tests/test_icp_gpu.py::test_schedule_is_invisible).
 int slam_icp_set_schedule(int probe_iters, int min_pairs) {
     if (probe_iters < -1 || min_pairs < 0) return fail(SLAM_EINVAL, "schedule: probe_iters < -1 or min_pairs < 0");
     g_sched_probe = probe_iters;

@@ -543,6 +543,52 @@ def test_gangs_are_bit_identical(k):
     assert np.array_equal(ro.tf, ro_single.tf) and np.array_equal(ro.err, ro_single.err)
 
 
+def test_rotation_only_is_bit_identical_on_every_tier(k):
+    """rotation_only=True through the team kernel, gangs of 2 and the wide tier
+    (one and two query groups per workgroup) equals the single launch bit for
+    bit, histories included: every kernel family takes the rotation-only branch
+    of the one shared update.  96 pairs of 361 points: six 64-query groups, the
+    last ragged (41 queries), so every pair has several exchange partners."""
+    from slamhip import _abi
+    lib = _abi.lib()
+    n = 96
+    seq, inits = _sequence_pairs(n, seed=12, n_beams=361)
+    src, dst = np.arange(1, n + 1), np.arange(0, n)
+
+    def run():
+        return k.icp_batch(seq.scans, src, dst, inits, epsilon=0.05, max_iters=7, rotation_only=True, history=True)
+
+    runs = {}
+    try:
+        assert lib.slam_icp_set_schedule(0, 1) == 0
+        single = run()
+        assert lib.slam_icp_set_schedule(-1, 1) == 0
+        lib.slam_icp_gang_timeouts()   # clear
+        for name, parts in (("teams", 0), ("gangs of 2", 2)):
+            assert lib.slam_icp_set_schedule_gangs(8, parts) == 0
+            runs[name] = run()
+            assert lib.slam_icp_gang_timeouts() == 0, name
+        assert lib.slam_icp_set_schedule_gangs(0, 4) == 0   # the wide tier alone
+        for groups in (1, 2):
+            assert lib.slam_icp_set_wide_groups(groups) == 0
+            assert lib.slam_icp_set_schedule_wide(8, 1) == 0
+            runs[f"wide, groups {groups}"] = run()
+            assert lib.slam_icp_gang_timeouts() == 0, groups
+    finally:
+        lib.slam_icp_set_wide_groups(1)
+        lib.slam_icp_set_schedule(-1, 1024)
+        lib.slam_icp_set_schedule_auto(1)
+    assert len(single.hist) == n
+    # the tiers take the 6 slowest-keyed pairs (one per 16) of those still running after the 3 probe iterations
+    assert (single.iters > 3).sum() >= 6
+    for key, r in runs.items():
+        assert np.array_equal(r.iters, single.iters), key
+        assert np.array_equal(r.tf, single.tf) and np.array_equal(r.err, single.err), key
+        assert len(r.hist) == len(single.hist), key
+        for h0, h1 in zip(single.hist, r.hist):
+            assert np.array_equal(h0, h1), key
+
+
 def test_gang_timeouts_are_repaired(k):
     """A gang part that waits too long for its partners stops without writing;
     after phase 2 the scheduler re-runs every unfinished gang pair on one
