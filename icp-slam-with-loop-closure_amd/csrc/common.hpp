@@ -289,6 +289,15 @@ __device__ __forceinline__ double wave_sum_exact16(double (&v)[16]) {
     return i == 0 ? t0 : i == 1 ? t1 : i == 2 ? t2 : t3;
 }
 
+// popcount(x) + acc in one instruction: left to itself the compiler counts every
+// dword into a register of its own and adds them up as a tree (8 + 7
+// instructions for a 32-byte descriptor instead of 8)
+__device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) {
+    uint32_t r;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
+    return r;
+}
+
 // A float's bits as an int of the same order (sign-magnitude -> two's
 // complement, an involution; -0 < +0, no NaN inputs), and back.
 __device__ __forceinline__ int f2ord(float f) {

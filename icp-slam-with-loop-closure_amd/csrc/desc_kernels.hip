@@ -59,15 +59,6 @@ __device__ __forceinline__ uint32_t dot4(uint32_t a, uint32_t b, uint32_t acc) {
     return __builtin_amdgcn_udot4(a, b, acc, false);
 }
 
-// popcount(x) + acc in one instruction: left to itself the compiler counts every
-// dword into a register of its own and adds them up as a tree (8 + 7
-// instructions for a descriptor instead of 8)
-__device__ __forceinline__ uint32_t bcnt(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
-}
-
 __device__ __forceinline__ uint32_t desc_norm(const Desc& v) {
     uint32_t s = dot4(v.lo.x, v.lo.x, 0);
     s = dot4(v.lo.y, v.lo.y, s);

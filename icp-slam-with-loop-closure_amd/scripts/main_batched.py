@@ -34,6 +34,13 @@ reference's selection and one ICP launch.  ``--image-match-error``,
 ``--keypoint-n-matches``, ``--image-downsample`` and ``--min-dist-along-path``
 feed it (scripts/main.py's defaults 2500 / 20 / 1 / 5 when unset) and
 ``--loop-closure-icp-error`` is its ICP threshold.
+``--loop-closure-detection signatures`` (new, opt-in; no counterpart in the
+reference) proposes the loop closures from the scans alone: rotation-invariant
+scan signatures matched on the GPU (slamhip.sig), the poses only excluding the
+recent path; ``--signature-sectors``, ``--signature-ring-width``,
+``--signature-min-dist-along-path``, ``--signature-max-frac NUM/DEN``,
+``--signature-icp-error`` and ``--signature-init signature|identity|csm``
+(default: the rotation the match found) feed it.
 Out of scope here (flags accepted, ignored): ORB keypoint extraction from
 images (OpenCV) and the matplotlib figures.
 
@@ -74,10 +81,23 @@ def parse(argv=None):
                         "reference's fixed 30")
     p.add_argument("--loop-closure-init", default="identity", choices=["identity", "csm"],
                    help="identity = the reference's ICP start (default); csm = correlative scan match of every pair")
-    p.add_argument("--loop-closure-detection", default="none", choices=["none", "proximity", "descriptors"],
+    p.add_argument("--loop-closure-detection", default="none",
+                   choices=["none", "proximity", "descriptors", "signatures"],
                    help="without --manual-loop-closures: none (default), proximity = the reference's "
-                        "detect_proximity with the candidate search on the GPU, or descriptors = its image "
-                        "detector from the ORB descriptors on, matched on the GPU")
+                        "detect_proximity with the candidate search on the GPU, descriptors = its image "
+                        "detector from the ORB descriptors on, matched on the GPU, or signatures = candidates "
+                        "from the scans' rotation-invariant signatures, matched on the GPU")
+    p.add_argument("--signature-sectors", default=64, type=int,
+                   help="signatures: angular sectors, a multiple of 8 in 8..128")
+    p.add_argument("--signature-ring-width", default=0.4, type=float, help="signatures: width of the 32 rings (m)")
+    p.add_argument("--signature-min-dist-along-path", default=5, type=float,
+                   help="signatures: least path length between the two scans of a candidate (m)")
+    p.add_argument("--signature-max-frac", default="1/4",
+                   help="signatures: NUM/DEN, a candidate differs in at most that share of the two scans' cells")
+    p.add_argument("--signature-icp-error", default=110, type=float,
+                   help="signatures: a candidate is accepted below this ICP error")
+    p.add_argument("--signature-init", default="signature", choices=["signature", "identity", "csm"],
+                   help="signatures: ICP start: the rotation the match found (default), identity or csm")
     p.add_argument("--descriptors", help="descriptors: an .npz with desc (D, 32) uint8 and off (M + 1) int64, or "
                                          "'auto' for a synthetic loop dataset")
     p.add_argument("--descriptor-metric", default="hamming", choices=["hamming", "l2"],
@@ -118,6 +138,15 @@ def parse(argv=None):
         p.error("starting after scan matching needs --pose-graph")
     if a.loop_closure_detection == "descriptors" and not a.descriptors:
         p.error("--loop-closure-detection descriptors needs --descriptors FILE.npz (or auto)")
+    try:
+        num, den = (int(v) for v in a.signature_max_frac.split("/"))
+        if not 0 <= num <= den or den < 1:
+            raise ValueError
+        a.signature_max_frac = (num, den)
+    except ValueError:
+        p.error("--signature-max-frac NUM/DEN with integers 0 <= NUM <= DEN, DEN >= 1 expected")
+    if not (8 <= a.signature_sectors <= 128 and a.signature_sectors % 8 == 0 and a.signature_ring_width > 0):
+        p.error("--signature-sectors a multiple of 8 in 8..128 and --signature-ring-width > 0 expected")
     if not (a.csm_window_m >= 0 and 0 < a.csm_angle_step_deg and 0 <= a.csm_angle_window_deg <= 180):
         p.error("--csm-window-m >= 0, --csm-angle-step-deg > 0 and 0 <= --csm-angle-window-deg <= 180 expected")
     return a
@@ -234,6 +263,16 @@ def run(a):
             report["loop_closure_detection"] = {"method": "descriptors", "metric": a.descriptor_metric,
                                                 "selected": len(good), "accepted": int(ok.sum()),
                                                 "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
+        elif a.manual_loop_closures is None and a.loop_closure_detection == "signatures":
+            from slamhip.sig import SigParams
+            t0 = time.perf_counter()
+            cand, ok = pipeline.signature_loop_closures(
+                pg, scans, a.signature_min_dist_along_path, a.signature_max_frac, a.signature_icp_error,
+                init=a.signature_init, csm=csm_params(a) if a.signature_init == "csm" else None,
+                params=SigParams(sectors=a.signature_sectors, dr=a.signature_ring_width))
+            report["loop_closure_detection"] = {"method": "signatures", "candidates": len(cand),
+                                                "accepted": int(ok.sum()), "init": a.signature_init,
+                                                "s": round(time.perf_counter() - t0, 3)}
         elif a.manual_loop_closures is None:
             print("image-based loop closure detection from images needs OpenCV (out of scope; see "
                   "--loop-closure-detection descriptors); no loop closures added",

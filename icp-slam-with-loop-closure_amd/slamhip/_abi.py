@@ -80,6 +80,12 @@ SIGNATURES = {
                                       c_ptr, c_ptr]),
     "slam_desc_status": (c_int, [c_ptr]),
     "slam_desc_set_bwd": (c_int, [c_int]),
+    "slam_sig_build": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "slam_sig_work_size": (c_i64, [c_int, c_int, c_int]),
+    "slam_sig_match": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
+                               c_ptr, c_ptr, c_ptr, c_ptr]),
+    "slam_sig_status": (c_int, [c_ptr]),
+    "slam_sig_set_screen": (c_int, [c_int]),
     "slam_gn_bcr_block_rows": (c_int, [c_int, c_int]),
     "slam_gn_iteration_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

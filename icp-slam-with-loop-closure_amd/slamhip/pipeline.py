@@ -13,7 +13,9 @@ The reference runs its hot path from ``scripts/main.py``:
   on the GPU (``proximity_loop_closures``); or, opt-in, its image detector
   (``:81-163``) from the ORB descriptors on, every image pair matched on the
   GPU (``image_loop_closures``; extracting the keypoints needs OpenCV and
-  stays out of scope);
+  stays out of scope); or, opt-in and without a counterpart in the reference,
+  candidates from the scans' own rotation-invariant signatures
+  (``signature_loop_closures``, ``slamhip.sig``);
 * stage 3, optimisation (``scripts/main.py:322-334``): ``optimization_max_iters``
   SGD steps with learning rate 1/(k+1), then the orientation recompute.
 
@@ -145,6 +147,54 @@ def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1,
     r = batch.result()
     used = set()
     for b, (i, j) in enumerate(cand):
+        if i in used or j in used:
+            continue
+        if float(r.err[b]) < err_thresh:
+            add_loop_constraint(pg, i, j, r.tf[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
+            used.update((i, j))
+            accepted[b] = True
+    return cand, accepted
+
+
+SIGNATURE_LOOP_CLOSURE_INITS = LOOP_CLOSURE_INITS + ("signature",)
+
+
+def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1, 4), err_thresh=110, max_iters=100,
+                            epsilon=0.05, scanset=None, init="signature", csm=None, params=None):
+    """Stage 2 from the scans alone (new; the reference has no counterpart):
+    the shape of ``proximity_loop_closures`` with the candidates of
+    ``slamhip.sig`` — for every scan i the scan j, at least
+    ``min_dist_along_path`` further along the path, whose rotation-invariant
+    signature is closest, kept when ``d_ij <= max_frac (n_i + n_j)``.  The
+    poses only exclude the recent path, so a loop that drift has opened wide is
+    proposed all the same.  Every candidate's icp(pc_j, pc_i) runs in ONE launch
+    over the resident ``scanset``, then the same greedy pass and the "relative"
+    convention.  ``init="signature"`` (the default here, and only here) starts
+    every ICP from the pure rotation by -2 pi k_ij / S of the best shift;
+    ``"identity"`` and ``"csm"`` as elsewhere.  ``params``: the
+    ``slamhip.sig.SigParams``.  For revisits in the direction of travel (at any
+    rotation of the scan frame): see ``slamhip.sig``.  Returns the candidates, a
+    list of (i, j, k) in the order the pass visits them, and the boolean mask
+    of those accepted."""
+    from . import icp as _icp
+    from . import sig as _sig
+    if init not in SIGNATURE_LOOP_CLOSURE_INITS:
+        raise ValueError(f"unknown loop-closure init {init!r} ({' | '.join(SIGNATURE_LOOP_CLOSURE_INITS)})")
+    params = params if params is not None else _sig.SigParams()
+    ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
+    cand = _sig.signature_candidates_device(ss, pg.poses, min_dist_along_path, params, max_frac)
+    accepted = np.zeros(len(cand), dtype=bool)
+    if not cand:
+        return cand, accepted
+    triples = np.asarray(cand, dtype=np.int64)
+    src, dst = triples[:, 1], triples[:, 0]   # icp(pc_j, pc_i), as the proximity stage
+    inits = _sig.shift_inits(triples[:, 2], params.sectors) if init == "signature" else \
+        loop_closure_inits(ss, src, dst, init, csm)
+    batch = _icp.IcpBatch(ss, src, dst, inits, epsilon=epsilon, max_iters=max_iters)
+    batch.launch()
+    r = batch.result()
+    used = set()
+    for b, (i, j, _) in enumerate(cand):
         if i in used or j in used:
             continue
         if float(r.err[b]) < err_thresh:

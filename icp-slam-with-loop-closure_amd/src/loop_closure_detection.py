@@ -34,6 +34,10 @@ approximates, ``False`` -> cross-checked ``hamming``), the selection and the ICP
 run as ``slamhip.pipeline.image_loop_closures``; with ``descriptors=`` (one
 (n, 32) uint8 array per image) OpenCV is not needed at all.  The default
 ``matcher="opencv"`` is the path above.
+
+New function: ``detect_signatures`` proposes loop closures from the scans
+themselves (rotation-invariant signatures matched on the GPU, ``slamhip.sig``),
+needing neither nearly right poses nor a camera.
 """
 import numpy as np
 import scipy.spatial
@@ -112,6 +116,21 @@ def detect_proximity(pose_graph, lidar_points, min_dist_along_path=2, max_dist=1
             # icp(pc_j, pc_i): X_j = X_i T, the "relative" convention (src/pose_graph.py)
             add_loop_constraint(pose_graph, i, j, res.tf[b].copy(), "relative")
             used.update((i, j))
+
+
+def detect_signatures(pose_graph, lidar_points, min_dist_along_path=5, max_frac=(1, 4), err_thresh=110,
+                      init="signature", csm=None, params=None):
+    """New, without a counterpart in the reference: loop closures from the scans
+    alone, beside ``detect_proximity`` and with its shape.  Every scan's best
+    rotation-invariant signature match at least ``min_dist_along_path`` further
+    along the path (``slamhip.sig``, searched on the GPU; the poses are not
+    asked for nearness), icp(pc_j, pc_i) of all of them in one launch from the
+    rotation the match found, and the same greedy pass
+    (``slamhip.pipeline.signature_loop_closures``).  For revisits in the
+    direction of travel, at any rotation of the scan frame."""
+    from slamhip.pipeline import signature_loop_closures
+    signature_loop_closures(pose_graph, lidar_points, min_dist_along_path, max_frac, err_thresh, init=init, csm=csm,
+                            params=params)
 
 
 def serialize_keypoints(kp, des):

@@ -397,6 +397,68 @@ int slam_desc_status(void* stream);
  * thread; identical results. */
 int slam_desc_set_bwd(int mode);
 
+/* ---- scan signatures (csrc/sig_kernels.hip) ---------------------------------
+ * Loop-closure candidates from the scans themselves: a rotation-invariant
+ * polar occupancy signature per scan and an all-pairs search over every
+ * rotation.  The reference has no counterpart (its detectors need nearly right
+ * poses or a camera); new since ABI 105.  The detector is for revisits in the
+ * direction of travel at any rotation of the scan frame: a 270-degree scan
+ * taken at a truly different heading sees other walls and is not matched.
+ *
+ * Parameters: S sectors, 8 <= S <= 128 and a multiple of 8; 32 rings;
+ *   dirs      float64[S][2]  (cos, sin) of the sector centres (s + 0.5) 2 pi /
+ *             S, evaluated by the caller (np.cos / np.sin, one scalar call each)
+ *   edges2    float64[33]    squared ring edges (r_min + k dr)^2, nondecreasing
+ * Signature of scan m (points pts[scan_off[m] .. scan_off[m + 1]) of the
+ * packed float64[P][2] array of slam_icp_batch_f64): for every point (x, y),
+ * r2 = (x x) + (y y) with three roundings (no FMA contraction); its ring is
+ * the r with edges2[r] <= r2 < edges2[r + 1], and a point outside every ring
+ * (or with a NaN coordinate) is dropped; its sector is the smallest s that
+ * maximises (c_s x) + (s_s y), three roundings again (no atan2).
+ *   sig       uint32[N][S]   bit r of sig[m][s] set when a point of scan m
+ *             fell into (ring r, sector s)
+ *   ring      uint8[N][32]   ring[m][r] = the number of sectors with bit r
+ *             set; 16-byte aligned
+ *   n_bits    int32[N]       their sum
+ * A scan whose offsets descend or leave [0, P] gets the empty signature and
+ * raises a flag (slam_sig_status).  SLAM_EINVAL for a null array, N < 0,
+ * P < 0, a bad S or a misaligned ring; N == 0 succeeds without a launch. */
+int slam_sig_build(const double* pts, const int64_t* scan_off, int32_t N, int64_t P, const double* dirs,
+                   const double* edges2, int32_t S, uint32_t* sig, uint8_t* ring, int32_t* n_bits, void* stream);
+/* Distance: d(i, j, k) = sum_s popcount(sig_i[s] xor sig_j[(s + k) mod S]);
+ * d_ij is its minimum over k in [0, S) and k_ij the smallest k that attains
+ * it (scan j's frame is turned by -2 pi k_ij / S against scan i's: the
+ * rotation by -2 pi k_ij / S is the initial guess of icp(pc1 = scan j, pc2 =
+ * scan i)).  For a row i < n_rows, scan j in [start[i], N) is a candidate iff
+ * d_ij den <= num (n_i + n_j), compared in 64-bit integers.
+ *   start      int32[n_rows]  0 <= start[i] <= N (N: no column); a start
+ *              outside raises a flag (slam_sig_status) and its row is empty
+ *   num, den   the threshold as a fraction, 0 <= num <= den, den >= 1
+ *   K          1..16
+ *   out_j, out_d, out_k  int32[n_rows][K]  the K smallest candidates by
+ *              (d_ij, j) ascending: j, d_ij, k_ij; unused slots are -1
+ *   out_count  int32[n_rows]  the number of candidates (may exceed K)
+ *   work       slam_sig_work_size(N, S, K) BYTES, 8-byte aligned, linear in N
+ *              (at most 16 column chunks of K partial entries per scan)
+ * Exact screen: LB_ij = sum_r |ring_i[r] - ring_j[r]| <= d_ij (per ring,
+ * popcount(a xor b) >= |popcount a - popcount b|, and a rotation keeps a
+ * ring's popcount), so a pair with LB_ij den > num (n_i + n_j) is skipped
+ * without changing any output.  Only integers decide anything: every launch
+ * shape gives the same bits.  Stream-ordered, graph-capturable, no host
+ * copies, nothing allocated.  SLAM_EINVAL for a null array, N <= 0, a bad S,
+ * K or threshold, n_rows outside [0, N] or a misaligned ring / work;
+ * n_rows == 0 succeeds without a launch.  slam_sig_status synchronises
+ * `stream`, reports the flags of every launch since the previous call
+ * (SLAM_OK or SLAM_EINVAL) and clears them. */
+int64_t slam_sig_work_size(int32_t N, int32_t S, int32_t K);
+int slam_sig_match(const uint32_t* sig, const uint8_t* ring, const int32_t* n_bits, int32_t N, int32_t S,
+                   const int32_t* start, int32_t n_rows, int32_t num, int32_t den, int32_t K, int32_t* out_j,
+                   int32_t* out_d, int32_t* out_k, int32_t* out_count, void* work, void* stream);
+int slam_sig_status(void* stream);
+/* Diagnostics: the ring-count screen on (1, default) or off (0: every pair is
+ * evaluated).  Per host thread; identical results. */
+int slam_sig_set_screen(int on);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
