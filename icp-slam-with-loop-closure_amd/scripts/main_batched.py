@@ -41,6 +41,11 @@ recent path; ``--signature-sectors``, ``--signature-ring-width``,
 ``--signature-min-dist-along-path``, ``--signature-max-frac NUM/DEN``,
 ``--signature-icp-error`` and ``--signature-init signature|identity|csm``
 (default: the rotation the match found) feed it.
+``--loop-closure-consistency`` (new, opt-in) checks the loop closures against
+each other at the end of the stage and removes those outside the pairwise
+consistent set (slamhip.pcm); ``--consistency-trans-tol``,
+``--consistency-rot-tol``, ``--consistency-trans-drift`` and
+``--consistency-rot-drift`` are its tolerances.
 Out of scope here (flags accepted, ignored): ORB keypoint extraction from
 images (OpenCV) and the matplotlib figures.
 
@@ -98,6 +103,17 @@ def parse(argv=None):
                    help="signatures: a candidate is accepted below this ICP error")
     p.add_argument("--signature-init", default="signature", choices=["signature", "identity", "csm"],
                    help="signatures: ICP start: the rotation the match found (default), identity or csm")
+    p.add_argument("--loop-closure-consistency", action="store_true",
+                   help="check the loop closures against each other at the end of the loop-closure stage and remove "
+                        "those outside the pairwise consistent set (slamhip.pcm)")
+    p.add_argument("--consistency-trans-tol", default=None, type=float,
+                   help="consistency: floor of a cycle's translation (m)")
+    p.add_argument("--consistency-rot-tol", default=None, type=float,
+                   help="consistency: floor of the chord of a cycle's rotation")
+    p.add_argument("--consistency-trans-drift", default=None, type=float,
+                   help="consistency: translation drift per square root of a chain step (m)")
+    p.add_argument("--consistency-rot-drift", default=None, type=float,
+                   help="consistency: rotation drift (chord) per square root of a chain step")
     p.add_argument("--descriptors", help="descriptors: an .npz with desc (D, 32) uint8 and off (M + 1) int64, or "
                                          "'auto' for a synthetic loop dataset")
     p.add_argument("--descriptor-metric", default="hamming", choices=["hamming", "l2"],
@@ -145,11 +161,22 @@ def parse(argv=None):
         a.signature_max_frac = (num, den)
     except ValueError:
         p.error("--signature-max-frac NUM/DEN with integers 0 <= NUM <= DEN, DEN >= 1 expected")
+    if any(v is not None and not v >= 0 for v in (a.consistency_trans_tol, a.consistency_rot_tol,
+                                                  a.consistency_trans_drift, a.consistency_rot_drift)):
+        p.error("--consistency-* tolerances >= 0 expected")
     if not (8 <= a.signature_sectors <= 128 and a.signature_sectors % 8 == 0 and a.signature_ring_width > 0):
         p.error("--signature-sectors a multiple of 8 in 8..128 and --signature-ring-width > 0 expected")
     if not (a.csm_window_m >= 0 and 0 < a.csm_angle_step_deg and 0 <= a.csm_angle_window_deg <= 180):
         p.error("--csm-window-m >= 0, --csm-angle-step-deg > 0 and 0 <= --csm-angle-window-deg <= 180 expected")
     return a
+
+
+def consistency_params(a):
+    """PcmParams of the --consistency-* flags, its defaults where unset."""
+    from slamhip.pcm import PcmParams
+    flags = dict(trans_tol=a.consistency_trans_tol, rot_tol=a.consistency_rot_tol,
+                 trans_drift=a.consistency_trans_drift, rot_drift=a.consistency_rot_drift)
+    return PcmParams(**{k: v for k, v in flags.items() if v is not None})
 
 
 def csm_params(a):
@@ -290,6 +317,13 @@ def run(a):
                                                csm=csm_params(a) if a.loop_closure_init == "csm" else None)
             report["loop_closures"] = {"annotated": int(len(matches)), "accepted": int(ok.sum()),
                                        "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
+        if a.loop_closure_consistency:
+            t0 = time.perf_counter()
+            edges, keep, unverified, res = pipeline.verify_loop_closures(pg, consistency_params(a), details=True)
+            report["loop_closure_consistency"] = {"closures": len(edges), "kept": int(keep.sum()),
+                                                  "removed": int(len(edges) - keep.sum()), "unverified": unverified,
+                                                  "steps": res.steps if res is not None else 0,
+                                                  "seconds": round(time.perf_counter() - t0, 3)}
         pg.save(out("loop_closure_pose_graph.pickle"))
         pg.export_g2o(out("loop_closure_pose_graph.g2o"))
     if a.program_end == "loop_closure":

@@ -86,6 +86,12 @@ SIGNATURES = {
                                c_ptr, c_ptr, c_ptr, c_ptr]),
     "slam_sig_status": (c_int, [c_ptr]),
     "slam_sig_set_screen": (c_int, [c_int]),
+    "slam_pcm_work_size": (c_i64, [c_int]),
+    "slam_pcm_adjacency_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_ptr,
+                                       c_ptr, c_ptr, c_ptr]),
+    "slam_pcm_select": (c_int, [c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "slam_pcm_status": (c_int, [c_ptr]),
+    "slam_pcm_set_peel_slots": (c_int, [c_int]),
     "slam_gn_bcr_block_rows": (c_int, [c_int, c_int]),
     "slam_gn_iteration_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

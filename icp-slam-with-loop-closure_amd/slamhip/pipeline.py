@@ -15,7 +15,9 @@ The reference runs its hot path from ``scripts/main.py``:
   GPU (``image_loop_closures``; extracting the keypoints needs OpenCV and
   stays out of scope); or, opt-in and without a counterpart in the reference,
   candidates from the scans' own rotation-invariant signatures
-  (``signature_loop_closures``, ``slamhip.sig``);
+  (``signature_loop_closures``, ``slamhip.sig``); then, opt-in and without a
+  counterpart either, the closures checked against each other and the
+  inconsistent ones removed (``verify_loop_closures``, ``slamhip.pcm``);
 * stage 3, optimisation (``scripts/main.py:322-334``): ``optimization_max_iters``
   SGD steps with learning rate 1/(k+1), then the orientation recompute.
 
@@ -261,6 +263,42 @@ def add_loop_constraint(pg, i, j, T, convention):
         pg.add_constraint(i, j, T, convention=convention)
     except TypeError:
         pg.add_constraint(i, j, T)
+
+
+def verify_loop_closures(pg, params=None, remove=True, details=False):
+    """Checks the loop closures of ``pg`` against each other (new, opt-in;
+    ``slamhip.pcm``: pairwise consistency over the chain ``pg.poses`` as they
+    stand, that is before optimisation) and removes the rejected edges
+    (``pg.remove_constraint``) unless ``remove`` is false.  The closures are
+    the edges added by ``add_constraint`` that carry a convention, in networkx
+    order; an "icp" edge (i, j, T), X_i = X_j T, is checked as (a = j, b = i,
+    Z = T).  ``params``: the ``slamhip.pcm.PcmParams``.  Returns the edges as a
+    list of (i, j, T), the boolean mask of those kept, and the number of
+    constraint edges without a convention, which stay in place unverified;
+    with ``details`` also the ``slamhip.pcm.PcmResult`` (None without a closure)."""
+    from . import pcm as _pcm
+    _, conv, added = pg.edge_kinds()
+    edges, a, b = [], [], []
+    for (i, j, T), c in zip(pg.graph.edges(data="object"), conv):
+        if c == 1:      # "icp"
+            a.append(j)
+            b.append(i)
+        elif c == 2:    # "relative"
+            a.append(i)
+            b.append(j)
+        else:
+            continue
+        edges.append((i, j, T))
+    unverified = int((added & (conv == 0)).sum())
+    res, keep = None, np.zeros(0, dtype=bool)
+    if edges:
+        res = _pcm.consistency(pg.poses, a, b, np.stack([T for _, _, T in edges]), params)
+        keep = res.keep
+    if remove:
+        for (i, j, _), ok in zip(edges, keep):
+            if not ok:
+                pg.remove_constraint(i, j)
+    return (edges, keep, unverified, res) if details else (edges, keep, unverified)
 
 
 def optimize(pg, lidar_points, optimization_max_iters=50, icp_max_iters=100, icp_epsilon=0.05,

@@ -38,6 +38,10 @@ run as ``slamhip.pipeline.image_loop_closures``; with ``descriptors=`` (one
 New function: ``detect_signatures`` proposes loop closures from the scans
 themselves (rotation-invariant signatures matched on the GPU, ``slamhip.sig``),
 needing neither nearly right poses nor a camera.
+
+New function: ``filter_consistent`` checks the loop closures the detectors
+added against each other and removes those outside the pairwise consistent set
+(``slamhip.pcm``, on the GPU), before the optimisation sees them.
 """
 import numpy as np
 import scipy.spatial
@@ -131,6 +135,17 @@ def detect_signatures(pose_graph, lidar_points, min_dist_along_path=5, max_frac=
     from slamhip.pipeline import signature_loop_closures
     signature_loop_closures(pose_graph, lidar_points, min_dist_along_path, max_frac, err_thresh, init=init, csm=csm,
                             params=params)
+
+
+def filter_consistent(pose_graph, params=None, remove=True):
+    """New, without a counterpart in the reference: checks the loop closures
+    the detectors above added against each other and removes those outside the
+    pairwise consistent set (``slamhip.pipeline.verify_loop_closures``,
+    ``slamhip.pcm``; on the GPU).  Call it before the optimisation.  Returns
+    the edges (i, j, T), the mask of those kept and the number of constraint
+    edges without a recorded convention, which stay unverified."""
+    from slamhip.pipeline import verify_loop_closures
+    return verify_loop_closures(pose_graph, params, remove)
 
 
 def serialize_keypoints(kp, des):

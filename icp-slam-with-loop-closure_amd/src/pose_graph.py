@@ -75,6 +75,12 @@ class PoseGraph():
             attrs["convention"] = convention
         self._flat = None
 
+    def remove_constraint(self, i, j):
+        """Removes the edge i -> j (new; ``networkx.NetworkXError`` when there
+        is none) and drops the caches, as ``invalidate()`` does."""
+        self.graph.remove_edge(i, j)
+        self.invalidate()
+
     def flip(self):
         """Reverse node order (theta + pi) and remap every edge a->b to
         (n-b)->(n-a); the pose array is reversed as a view, as in the reference.

@@ -459,6 +459,67 @@ int slam_sig_status(void* stream);
  * evaluated).  Per host thread; identical results. */
 int slam_sig_set_screen(int on);
 
+/* ---- pairwise consistency of loop closures (csrc/pcm_kernels.hip) -------------
+ * Verifies the loop closures against each other before they reach an
+ * optimiser (pairwise consistent measurement set selection): two closures are
+ * consistent when the cycle they form with the chain of poses closes to within
+ * the chain's drift, and a large pairwise consistent set is kept.  The reference
+ * has no counterpart; new since ABI 106.
+ *
+ * An SE(2) element is four doubles (c, s, x, y).  Every operation below is
+ * individually rounded (no FMA contraction):
+ *   mul(A, B): c = A.c B.c - A.s B.s          s = A.s B.c + A.c B.s
+ *              x = (A.c B.x - A.s B.y) + A.x  y = (A.s B.x + A.c B.y) + A.y
+ *   inv(A):    c = A.c   s = -A.s   x = -(A.c A.x + A.s A.y)   y = A.s A.x - A.c A.y
+ *   X      float64[N][4]  the chain poses, (cos, sin) evaluated by the caller
+ *          (np.cos / np.sin, one scalar call each): no transcendental here
+ *   a, b   int32[L]       closure l measures X_b = X_a Z ("relative" convention)
+ *   Z      float64[L][4]
+ * Per closure: V = X[a], D = mul(mul(V, Z), inv(X[b])), Di = inv(D), U =
+ * mul(inv(V), D).  Per unordered pair l < m: E = mul(mul(U_l, Di_m), V_l) (the
+ * cycle a_l -> b_l -> b_m -> a_m -> a_l in a_l's frame), n = |a_l - a_m| +
+ * |b_l - b_m|, dt = E.x E.x + E.y E.y, dr = E.s E.s + (1 - E.c)(1 - E.c); the
+ * pair is consistent iff dt <= trans_tol^2 + (trans_drift^2) n and dr <=
+ * rot_tol^2 + (rot_drift^2) n (a floor plus random-walk growth, in variance
+ * form).  A NaN compares false: such a closure is consistent with nothing.
+ *   out_adj  uint32[L][W], W = ceil(L / 32): bit m of row l is bit m & 31 of
+ *            word m >> 5; bits (l, m) and (m, l) both come from the pair
+ *            evaluated as (min, max), the diagonal and the bits past L are 0
+ *   out_deg  int32[L]      the rows' popcounts
+ *   work     slam_pcm_work_size(L) BYTES, 8-byte aligned (96 per closure)
+ * An a or b outside [0, N) raises a flag (slam_pcm_status); it is never read
+ * through and its row and column are empty.
+ *
+ * slam_pcm_select is a min-degree peel: with every closure alive, repeat: take
+ * the alive closure of the lowest degree, on ties the HIGHEST index; if its
+ * degree is the number of the others alive, they are a clique: stop; otherwise
+ * remove it (out_order = the step, from 0) and decrement its alive neighbours.
+ *   out_order  int32[L]   the removal step, -1 for a closure never removed
+ *   out_keep   uint8[L]   1 for the closures left, all 0 when fewer than
+ *              min_size are left
+ *   out_steps  int32[1]   the number of removals
+ * deg is only read.  The result is A maximal consistent set, not the maximum
+ * one.  One workgroup; a step costs one block minimum and one bit row.
+ *
+ * Stream-ordered, graph-capturable, no host copies, nothing allocated.
+ * SLAM_EINVAL for a null array, L < 0, N <= 0, min_size < 0, a negative
+ * tolerance or a misaligned work; SLAM_ETOOBIG for L > 65,536 (a 512 MB
+ * matrix; index and degree are 16-bit fields of the peel's keys); L == 0
+ * succeeds without a launch.  slam_pcm_status synchronises `stream`, reports
+ * the flag of every launch since the previous call (SLAM_OK or SLAM_EINVAL)
+ * and clears it. */
+int64_t slam_pcm_work_size(int32_t L);
+int slam_pcm_adjacency_f64(const double* X, int32_t N, const int32_t* a, const int32_t* b, const double* Z, int32_t L,
+                           double trans_tol, double trans_drift, double rot_tol, double rot_drift, uint32_t* out_adj,
+                           int32_t* out_deg, void* work, void* stream);
+int slam_pcm_select(const uint32_t* adj, const int32_t* deg, int32_t L, int32_t min_size, int32_t* out_order,
+                    uint8_t* out_keep, int32_t* out_steps, void* stream);
+int slam_pcm_status(void* stream);
+/* Diagnostics: closures per thread of the peel's one workgroup: 0 (default)
+ * the smallest of 1, 4, 16, 64 that covers L, or one of them as the least
+ * (four instantiations of one kernel).  Per host thread; identical results. */
+int slam_pcm_set_peel_slots(int slots);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
