@@ -688,6 +688,65 @@ int slam_pgo_sgd_stamps(unsigned long long* out8) {
 #endif
 }
 
+// The relaxation's launch for N poses: the ONLY place that decides it
+// (slam_pgo_sgd_step_f64 launches what this returns, slam_pgo_sgd_plan reports
+// it).  Automatic: poses in LDS (one wave) up to kLdsPoses, whole-block updates
+// in BR rounds of 64 blocks; the lazy-offset block size 2^sh is >= 64 nodes and
+// grows until at most kMaxOffBlocks blocks remain.  slam_pgo_sgd_force
+// overrides the path and, on the workgroup path, sh (tests); a forced setting
+// that cannot hold the graph is an error, never a different launch.
+struct SgdPlan {
+    int in_lds, rounds, shift, threads;
+};
+static thread_local int g_sgd_path = -1;
+static thread_local int g_sgd_shift = -1;
+
+static int sgd_plan(int32_t N, SgdPlan* p) {
+    if (N < 1) return fail(SLAM_EINVAL, "sgd plan: N=%d", N);
+    auto blocks = [&](int sh) { return ((N - 1) >> sh) + 1; };
+    int sh = 6;
+    while (blocks(sh) > kMaxOffBlocks) ++sh;
+    const int path = g_sgd_path >= 0 ? g_sgd_path : (N > kLdsPoses ? 2 : (blocks(sh) <= 64 ? 0 : 1));
+    if (g_sgd_shift >= 0) sh = g_sgd_shift;   // only ever set together with path 2
+    static_assert(((kLdsPoses - 1) >> 6) + 1 <= 2 * 64, "BR = 2 covers every LDS-resident graph");
+    if (path < 2) {
+        // one wave: kRelaxSlots x 64 = 128 explicit-node slots, so 2^sh = 64
+        const int br = path + 1;
+        if (N > kLdsPoses) return fail(SLAM_EINVAL, "sgd: forced LDS path holds %d poses, N=%d", kLdsPoses, N);
+        if (blocks(6) > 64 * br)
+            return fail(SLAM_EINVAL, "sgd: forced BR=%d covers %d blocks, N=%d has %d", br, 64 * br, N, blocks(6));
+        *p = SgdPlan{1, br, 6, relax_threads<true>()};
+    } else {
+        if (blocks(sh) > kMaxOffBlocks)
+            return fail(SLAM_EINVAL, "sgd: forced shift %d gives %d blocks of N=%d, at most %d", sh, blocks(sh), N,
+                        kMaxOffBlocks);
+        *p = SgdPlan{0, 1, sh, relax_threads<false>()};
+    }
+    return ok();
+}
+
+int slam_pgo_sgd_plan(int32_t N, int32_t* in_lds, int32_t* rounds, int32_t* shift, int32_t* threads) {
+    SgdPlan p;
+    const int rc = sgd_plan(N, &p);
+    if (rc != SLAM_OK) return rc;
+    if (in_lds) *in_lds = p.in_lds;
+    if (rounds) *rounds = p.rounds;
+    if (shift) *shift = p.shift;
+    if (threads) *threads = p.threads;
+    return ok();
+}
+
+int slam_pgo_sgd_force(int32_t path, int32_t shift) {
+    if (path < -1 || path > 2) return fail(SLAM_EINVAL, "sgd force: path %d not in {-1, 0, 1, 2}", path);
+    if (shift != -1 && (shift < 6 || shift > 12)) return fail(SLAM_EINVAL, "sgd force: shift %d not -1 or 6..12", shift);
+    if (shift != -1 && path != 2)
+        return fail(SLAM_EINVAL, "sgd force: shift %d needs path 2 (the one-wave kernel has 128 node slots: shift 6)",
+                    shift);
+    g_sgd_path = path;
+    g_sgd_shift = shift;
+    return ok();
+}
+
 int64_t slam_pgo_sgd_work_size(int32_t N, int32_t E) {
     // doubles: invM (3N) | dw (3E) | gamma (4) | C (3N+3) | TF (9E) | RT (3E) | then int32: A, B, IDX (E each) | K
     return 3 * static_cast<int64_t>(N) + 3 * static_cast<int64_t>(E) + 4 + 3 * (static_cast<int64_t>(N) + 1) +
@@ -700,6 +759,8 @@ int slam_pgo_sgd_step_f64(double* poses, int32_t N, const int32_t* ea, const int
     if (N < 0 || E < 0) return fail(SLAM_EINVAL, "sgd: N=%d E=%d", N, E);
     if (N == 0 || E == 0) return ok();
     if (!poses || !ea || !eb || !tf || !work) return fail(SLAM_EINVAL, "sgd: null array argument");
+    SgdPlan plan;   // before any launch: a forced setting that cannot hold the graph fails here
+    if (const int rc = sgd_plan(N, &plan); rc != SLAM_OK) return rc;
     hipStream_t s = as_stream(stream);
     double* invM = work;
     double* dw = work + 3 * static_cast<int64_t>(N);
@@ -719,16 +780,12 @@ int slam_pgo_sgd_step_f64(double* poses, int32_t N, const int32_t* ea, const int
                        invM);
     hipLaunchKernelGGL(sgd_prefix_kernel, dim3(1), dim3(kRelaxBlock), 0, s, invM, N, C);
     hipLaunchKernelGGL(sgd_irtw_kernel, dim3((E + 255) / 256), dim3(256), 0, s, A, Bv, Kp, C, E, RT);
-    // lazy-offset block size 2^sh: >= 64 nodes, at most kMaxOffBlocks blocks
-    int sh = 6;
-    while ((((N - 1) >> sh) + 1) > kMaxOffBlocks) ++sh;
+    const int sh = plan.shift;
     const size_t offb = 2 * 3 * static_cast<size_t>(((N - 1) >> sh) + 1) * sizeof(double);   // off + cA
-    if (N <= kLdsPoses) {
+    if (plan.in_lds) {
         // one wave; whole-block updates in BR rounds of 64 (nblk <= 96 here)
         const size_t lds = offb + 3 * static_cast<size_t>(N) * sizeof(double);
-        const int nblk = ((N - 1) >> sh) + 1;
-        auto kern = nblk <= 64 ? sgd_relax_kernel<true, 1> : sgd_relax_kernel<true, 2>;
-        static_assert(((kLdsPoses - 1) >> 6) + 1 <= 2 * 64, "BR = 2 covers every LDS-resident graph");
+        auto kern = plan.rounds == 1 ? sgd_relax_kernel<true, 1> : sgd_relax_kernel<true, 2>;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   static_cast<int>(lds));
         hipLaunchKernelGGL(kern, dim3(1), dim3(relax_threads<true>()), lds, s, poses, N, A, Bv, TF, RT, Kp, C,

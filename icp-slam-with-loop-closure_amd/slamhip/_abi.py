@@ -57,7 +57,10 @@ SIGNATURES = {
                                   c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "slam_kabsch2d_f64": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     "slam_pgo_sgd_work_size": (c_i64, [c_int, c_int]),
-    "slam_pgo_sgd_step_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_dbl, c_dbl, c_ptr, c_ptr]),
+    "slam_pgo_sgd_plan": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int),
+                                  ctypes.POINTER(c_int)]),
+    "slam_pgo_sgd_force": (c_int, [c_int, c_int]),
+    "slam_pgo_sgd_step_f64":(c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_int, c_dbl, c_dbl, c_ptr, c_ptr]),
     "slam_pgo_orient_f64": (c_int, [c_ptr, c_int, c_ptr]),
     "slam_pgo_orient_from_tf_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr]),
     "slam_gn_work_size": (c_i64, [c_int, c_int, c_int]),

@@ -46,6 +46,22 @@ class SgdSolver:
         return self.poses.cpu().numpy().reshape(self.N, 3)
 
 
+def sgd_plan(N):
+    """What the relaxation launches for N poses (host only, no GPU needed):
+    ``{"in_lds", "rounds", "shift", "threads"}`` of ``slam_pgo_sgd_plan``."""
+    import ctypes
+    v = [ctypes.c_int32() for _ in range(4)]
+    _abi.check(_abi.lib().slam_pgo_sgd_plan(int(N), *[ctypes.byref(x) for x in v]), "slam_pgo_sgd_plan")
+    return {"in_lds": bool(v[0].value), "rounds": v[1].value, "shift": v[2].value, "threads": v[3].value}
+
+
+def force_sgd_path(path=-1, shift=-1):
+    """Tests / diagnostics: force the relaxation's kernel (-1 automatic, 0 one
+    wave BR = 1, 1 one wave BR = 2, 2 workgroup) and, with path 2, the block
+    shift (6..12).  ``force_sgd_path()`` restores the automatic choice."""
+    _abi.check(_abi.lib().slam_pgo_sgd_force(int(path), int(shift)), "slam_pgo_sgd_force")
+
+
 def sgd_step(poses, ea, eb, tf, learning_rate=1.0, loop_closure_uncertainty=0.1):
     """One step; returns the updated (N, 3) array (a new host array)."""
     s = SgdSolver(poses, ea, eb, tf)

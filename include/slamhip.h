@@ -140,6 +140,29 @@ int slam_pgo_sgd_step_f64(double* poses, int32_t N, const int32_t* ea,
 int64_t slam_pgo_sgd_work_size(int32_t N, int32_t E);
 
 /*
+ * What slam_pgo_sgd_step_f64 launches for the relaxation of N >= 1 poses (host
+ * only; the step chooses its launch through the same function): *in_lds 1 =
+ * one wave with the poses in LDS, 0 = a workgroup with the poses in global
+ * memory; *rounds = whole-block update rounds of the one-wave kernel (BR, 1 or
+ * 2; 1 on the workgroup path); *shift = log2 of the lazy-offset block size;
+ * *threads = the launch's thread count.  Any output pointer may be NULL.
+ * Reports the forced plan while slam_pgo_sgd_force is active, SLAM_EINVAL if
+ * that setting cannot hold N poses.
+ */
+int slam_pgo_sgd_plan(int32_t N, int32_t* in_lds, int32_t* rounds, int32_t* shift, int32_t* threads);
+
+/*
+ * Diagnostics / tests: force the relaxation's launch.  path: -1 automatic, 0
+ * one wave BR = 1, 1 one wave BR = 2, 2 workgroup with global poses.  shift: -1
+ * automatic, or 6..12, accepted with path == 2 only (the one-wave kernel has
+ * 128 explicit-node slots: shift 6).  A step whose forced setting cannot hold
+ * its graph (N above the LDS pose capacity, more blocks than 64 * BR or than
+ * the lazy-offset table) returns SLAM_EINVAL before launching anything.  Per
+ * host thread; results agree to rounding between paths.
+ */
+int slam_pgo_sgd_force(int32_t path, int32_t shift);
+
+/*
  * Heading recompute from positions, in place.  Replaces the first loop of
  * src/pose_graph_optimization.py:51-57 `recompute_pose_graph_orientation`.
  */

@@ -50,6 +50,39 @@ def test_host_only_calls():
     rc = lib.slam_kabsch2d_f64(None, None, 0, None, None, None)
     assert rc == -1
     assert lib.slam_pgo_sgd_work_size(10, 4) >= 3 * 10 + 3 * 4
+    # the relaxation's launch plan: (in LDS, BR, shift, threads) per N, and the
+    # forced plans; a force that cannot hold the graph is an error, not another launch
+    from slamhip import pgo
+    one = lambda br: {"in_lds": True, "rounds": br, "shift": 6, "threads": 64}      # noqa: E731
+    wg = lambda sh: {"in_lds": False, "rounds": 1, "shift": sh, "threads": 256}     # noqa: E731
+    for N, want in [(1, one(1)), (3, one(1)), (4096, one(1)), (4097, one(2)), (6144, one(2)), (6145, wg(6)),
+                    (131072, wg(6)), (131073, wg(7)), (262144, wg(7)), (262145, wg(8)), (524288, wg(8)),
+                    (524289, wg(9))]:
+        assert pgo.sgd_plan(N) == want, N
+    assert lib.slam_pgo_sgd_plan(0, None, None, None, None) == -1
+    assert lib.slam_pgo_sgd_plan(100, None, None, None, None) == 0      # NULL outputs are allowed
+    try:
+        for bad in [(3, -1), (-2, -1), (0, 6), (1, 6), (-1, 6), (2, 5), (2, 13)]:
+            assert lib.slam_pgo_sgd_force(*bad) == -1 and lib.slam_last_error(), bad
+            assert pgo.sgd_plan(200) == one(1), bad      # a refused force changes nothing
+        pgo.force_sgd_path(0)
+        assert pgo.sgd_plan(4096) == one(1)
+        for N in (4097, 6145):
+            with pytest.raises(_abi.SlamHipError):
+                pgo.sgd_plan(N)
+        pgo.force_sgd_path(1)
+        assert pgo.sgd_plan(200) == one(2) and pgo.sgd_plan(6144) == one(2)
+        with pytest.raises(_abi.SlamHipError):
+            pgo.sgd_plan(6145)
+        pgo.force_sgd_path(2)
+        assert pgo.sgd_plan(200) == wg(6) and pgo.sgd_plan(131073) == wg(7)
+        pgo.force_sgd_path(2, 9)
+        assert pgo.sgd_plan(2200) == wg(9) and pgo.sgd_plan(2048 * 512) == wg(9)
+        with pytest.raises(_abi.SlamHipError):
+            pgo.sgd_plan(2048 * 512 + 1)
+    finally:
+        pgo.force_sgd_path()
+    assert pgo.sgd_plan(6145) == wg(6)
     n = lib.slam_icp_num_instances()
     assert n >= 4
     # instance chooser: smallest capacity covering the scan
