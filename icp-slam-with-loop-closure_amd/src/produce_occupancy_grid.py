@@ -21,6 +21,7 @@ Deviation (checked): kHitOdds and kMissOdds must be integers in [1, 127].
 Global points are rounded as the reference's per-point 3x3 @ 3x1 NumPy product
 rounds them on the build host (fma(a0, x0, a1 x1) + a2 x2), so grids and origins
 match the reference's own functions bit for bit (tests/golden/grid_ref.npz).
+Scans without a single point raise ValueError, as the reference's np.min does.
 """
 import struct
 import zlib
@@ -32,6 +33,9 @@ from slamhip import grid as _grid
 
 def produce_occupancy_grid(poses, lidar_points, cell_width, min_width=0, min_height=0, kHitOdds=3, kMissOdds=1):
     poses = np.asarray(poses, dtype=np.float64)
+    if sum(np.asarray(s).size for s in lidar_points) == 0:
+        # the reference's np.min over no points; the device bounds would be +-inf
+        raise ValueError("produce_occupancy_grid: the scans hold no point")
     m = _grid.OccupancyMapper(poses, lidar_points)
     _, b = m.global_points()
     min_x = b[0] - (cell_width / 2)

@@ -83,6 +83,26 @@ def test_host_only_calls():
     finally:
         pgo.force_sgd_path()
     assert pgo.sgd_plan(6145) == wg(6)
+    # the occupancy-grid update refuses bad arguments before any launch (all arrays NULL here,
+    # and the NULL check comes last): S, H, W, P, the odds, the cell width, the event-key range
+    def grid_update(S=1, P=10, cw=0.25, H=5, W=7, kh=3, km=1):
+        return lib.slam_grid_update_i8(None, None, S, None, P, 0.0, 0.0, cw, H, W, kh, km, None, None, None)
+    EINVAL, ETOOBIG = -1, -3
+    for kw, rc, word in [({"S": 0}, EINVAL, b"S=0"), ({"P": -1}, EINVAL, b"P=-1"), ({"H": 0}, EINVAL, b"H=0"),
+                         ({"W": 0}, EINVAL, b"W=0"), ({"kh": 0}, EINVAL, b"odds"), ({"kh": 128}, EINVAL, b"odds"),
+                         ({"km": 0}, EINVAL, b"odds"), ({"km": 128}, EINVAL, b"odds"),
+                         ({"cw": 0.0}, EINVAL, b"cell_width"), ({"cw": float("nan")}, EINVAL, b"cell_width"),
+                         ({"cw": -0.25}, EINVAL, b"cell_width"),
+                         ({"H": 1 << 21, "W": 1 << 21}, ETOOBIG, b"event-key"),
+                         ({"H": 1, "W": (1 << 22) - 1}, ETOOBIG, b"event-key"),
+                         ({"P": 1 << 40}, ETOOBIG, b"event-key"),
+                         ({}, EINVAL, b"null"), ({"P": 0}, EINVAL, b"null"),
+                         ({"H": 1, "W": (1 << 22) - 2, "P": (1 << 40) - 1, "kh": 127, "km": 127}, EINVAL, b"null")]:
+        assert grid_update(**kw) == rc and word in lib.slam_last_error(), (kw, lib.slam_last_error())
+    assert lib.slam_grid_global_points_f64(None, None, 0, None, None, None, None, None) == EINVAL
+    assert lib.slam_grid_global_points_f64(None, None, 3, None, None, None, None, None) == EINVAL
+    assert b"null" in lib.slam_last_error()
+    assert lib.slam_grid_work_size(3, 5, 7) >= 32 * 3 + 16 * 35
     n = lib.slam_icp_num_instances()
     assert n >= 4
     # instance chooser: smallest capacity covering the scan

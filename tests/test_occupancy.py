@@ -101,8 +101,8 @@ def test_oracle_vs_reference_fixtures(golden):
 @pytest.mark.gpu
 def test_produce_vs_reference_fixtures(golden):
     """The HIP mapper equals the reference's own grid functions bit for bit
-    (tests/golden/grid_ref.npz): grid, origin, and the update of an existing
-    grid with more scans."""
+    (tests/golden/grid_ref.npz): grid, origin, global points, and the update of
+    an existing grid with more scans."""
     import src.produce_occupancy_grid as pog
     g = golden("grid_ref.npz")
     for c in range(int(g["n_cases"])):
@@ -111,6 +111,7 @@ def test_produce_vs_reference_fixtures(golden):
                                                    kHitOdds=kh, kMissOdds=km)
         assert (mx, my) == tuple(g[f"origin_{c}"]), c
         assert got.dtype == np.int8 and np.array_equal(got, g[f"grid_{c}"]), c
+        assert np.array_equal(np.concatenate(pog.construct_global_points(poses, scans)), g[f"gpts_{c}"]), c
     poses, scans = _upd_case(g)
     grid = g["grid_0"].copy()
     pog.update_occupancy_grid(grid, poses, scans, 0.1, *g["origin_0"])
@@ -147,6 +148,10 @@ def test_update_min_size_and_global_points():
     gp = pog.construct_global_points(poses, scans)
     rp = oo.global_points(poses, scans)
     assert max(np.abs(a - b).max() for a, b in zip(gp, rp)) <= 1e-14
+    # bit for bit against the device's rule in rational arithmetic (no BLAS in it)
+    import grid_ref
+    for a, b in zip(gp, grid_ref.global_points_exact(poses, scans)):
+        assert np.array_equal(a, b)
 
 
 @pytest.mark.gpu
