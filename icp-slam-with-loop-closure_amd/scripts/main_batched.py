@@ -114,6 +114,14 @@ def parse(argv=None):
                    help="consistency: translation drift per square root of a chain step (m)")
     p.add_argument("--consistency-rot-drift", default=None, type=float,
                    help="consistency: rotation drift (chord) per square root of a chain step")
+    p.add_argument("--icp-refine", default="none", choices=["none", "point-to-line"],
+                   help="refine every ICP edge (scan matching and accepted loop closures) with the gated "
+                        "point-to-line metric of slamhip.plicp (new, opt-in; default: none)")
+    p.add_argument("--refine-max-dist", default=0.5, type=float, help="refinement: the correspondence gate (m)")
+    p.add_argument("--refine-min-overlap", default=0.5, type=float,
+                   help="refinement: an edge keeps its point-to-point transform below this share of inliers")
+    p.add_argument("--refine-min-observability", default=0.0, type=float,
+                   help="refinement: ... and below this observability of the translation (0: off)")
     p.add_argument("--descriptors", help="descriptors: an .npz with desc (D, 32) uint8 and off (M + 1) int64, or "
                                          "'auto' for a synthetic loop dataset")
     p.add_argument("--descriptor-metric", default="hamming", choices=["hamming", "l2"],
@@ -164,6 +172,9 @@ def parse(argv=None):
     if any(v is not None and not v >= 0 for v in (a.consistency_trans_tol, a.consistency_rot_tol,
                                                   a.consistency_trans_drift, a.consistency_rot_drift)):
         p.error("--consistency-* tolerances >= 0 expected")
+    if not (np.isfinite(a.refine_max_dist) and a.refine_max_dist >= 0 and 0 <= a.refine_min_overlap <= 1
+            and 0 <= a.refine_min_observability <= 1):
+        p.error("--refine-max-dist >= 0 and --refine-min-overlap, --refine-min-observability in [0, 1] expected")
     if not (8 <= a.signature_sectors <= 128 and a.signature_sectors % 8 == 0 and a.signature_ring_width > 0):
         p.error("--signature-sectors a multiple of 8 in 8..128 and --signature-ring-width > 0 expected")
     if not (a.csm_window_m >= 0 and 0 < a.csm_angle_step_deg and 0 <= a.csm_angle_window_deg <= 180):
@@ -177,6 +188,16 @@ def consistency_params(a):
     flags = dict(trans_tol=a.consistency_trans_tol, rot_tol=a.consistency_rot_tol,
                  trans_drift=a.consistency_trans_drift, rot_drift=a.consistency_rot_drift)
     return PcmParams(**{k: v for k, v in flags.items() if v is not None})
+
+
+def refine_params(a):
+    """(PlicpParams, gates) of the --icp-refine / --refine-* flags as the keywords
+    of the pipeline's stages; empty without a refinement."""
+    if a.icp_refine == "none":
+        return {}
+    from slamhip.plicp import PlicpParams
+    return {"refine": PlicpParams(max_dist=a.refine_max_dist),
+            "refine_gates": (a.refine_min_overlap, a.refine_min_observability)}
 
 
 def csm_params(a):
@@ -254,10 +275,14 @@ def run(a):
             pg = pose_graph.PoseGraph(odometry.copy())
             stem = "odometry_pose_graph"
         else:
-            r = pipeline.scan_matching(odometry, scans, a.icp_max_iters, a.icp_epsilon)
+            r = pipeline.scan_matching(odometry, scans, a.icp_max_iters, a.icp_epsilon, **refine_params(a))
             pg = pose_graph.PoseGraph(r.poses)
             stem = "icp_pose_graph"
             report["icp_mean_iters"] = float(np.mean(r.iters)) if len(r.iters) else 0.0
+            if r.refine_status is not None:
+                report["icp_refine"] = {"method": a.icp_refine, "edges": int(len(r.refine_status)),
+                                        "taken": int(r.refine_taken.sum()),
+                                        "status": np.bincount(r.refine_status, minlength=4).tolist()}
         report["scan_matching_s"] = round(time.perf_counter() - t0, 3)
         if not a.skip_icp:
             save_map(a, pg.poses, scans, "icp", report)
@@ -274,7 +299,8 @@ def run(a):
             t0 = time.perf_counter()
             cand, ok = pipeline.proximity_loop_closures(
                 pg, scans, a.proximity_min_dist_along_path, a.proximity_max_dist, a.proximity_icp_error,
-                init=a.loop_closure_init, csm=csm_params(a) if a.loop_closure_init == "csm" else None)
+                init=a.loop_closure_init, csm=csm_params(a) if a.loop_closure_init == "csm" else None,
+                **refine_params(a))
             report["loop_closure_detection"] = {"method": "proximity", "candidates": len(cand),
                                                 "accepted": int(ok.sum()), "init": a.loop_closure_init,
                                                 "s": round(time.perf_counter() - t0, 3)}
@@ -286,7 +312,7 @@ def run(a):
                 pg, scans, descriptors, ip["image_downsample"],
                 ip["min_dist_along_path"], ip["image_match_error"], ip["keypoint_n_matches"],
                 a.loop_closure_icp_error, metric=a.descriptor_metric, init=a.loop_closure_init,
-                csm=csm_params(a) if a.loop_closure_init == "csm" else None)
+                csm=csm_params(a) if a.loop_closure_init == "csm" else None, **refine_params(a))
             report["loop_closure_detection"] = {"method": "descriptors", "metric": a.descriptor_metric,
                                                 "selected": len(good), "accepted": int(ok.sum()),
                                                 "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
@@ -296,7 +322,7 @@ def run(a):
             cand, ok = pipeline.signature_loop_closures(
                 pg, scans, a.signature_min_dist_along_path, a.signature_max_frac, a.signature_icp_error,
                 init=a.signature_init, csm=csm_params(a) if a.signature_init == "csm" else None,
-                params=SigParams(sectors=a.signature_sectors, dr=a.signature_ring_width))
+                params=SigParams(sectors=a.signature_sectors, dr=a.signature_ring_width), **refine_params(a))
             report["loop_closure_detection"] = {"method": "signatures", "candidates": len(cand),
                                                 "accepted": int(ok.sum()), "init": a.signature_init,
                                                 "s": round(time.perf_counter() - t0, 3)}
@@ -314,7 +340,8 @@ def run(a):
                 matches = pipeline.read_manual_loop_closures(a.manual_loop_closures)
             t0 = time.perf_counter()
             ok = pipeline.manual_loop_closures(pg, scans, matches, init=a.loop_closure_init,
-                                               csm=csm_params(a) if a.loop_closure_init == "csm" else None)
+                                               csm=csm_params(a) if a.loop_closure_init == "csm" else None,
+                                               **refine_params(a))
             report["loop_closures"] = {"annotated": int(len(matches)), "accepted": int(ok.sum()),
                                        "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
         if a.loop_closure_consistency:

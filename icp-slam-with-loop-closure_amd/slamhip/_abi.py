@@ -95,6 +95,11 @@ SIGNATURES = {
     "slam_pcm_select": (c_int, [c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
     "slam_pcm_status": (c_int, [c_ptr]),
     "slam_pcm_set_peel_slots": (c_int, [c_int]),
+    "slam_plicp_normals_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_int, c_dbl, c_dbl, c_ptr, c_ptr]),
+    "slam_plicp_batch_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_dbl, c_int,
+                                     c_int, c_dbl, c_dbl, c_dbl, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                     c_ptr, c_int, c_ptr]),
+    "slam_plicp_status": (c_int, [c_ptr]),
     "slam_gn_bcr_block_rows": (c_int, [c_int, c_int]),
     "slam_gn_iteration_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -44,10 +44,41 @@ class ScanMatchResult:
     tf: np.ndarray         # (S-1, 3, 3) transforms[-1] of every pair (i, i-1)
     err: np.ndarray        # (S-1,) ICP errors
     iters: np.ndarray      # (S-1,) ICP iterations
+    refine_status: np.ndarray = None    # (S-1,) slamhip.plicp statuses of the point-to-line refinement (refine=...)
+    refine_inliers: np.ndarray = None   # (S-1,) its inliers
+    refine_obs: np.ndarray = None       # (S-1,) its observability
+    refine_taken: np.ndarray = None     # (S-1,) bool: the edges whose transform is the refined one
 
 
-def scan_matching(odometry, lidar_points, icp_max_iters=100, icp_epsilon=0.05, scanset=None):
-    """Stage 1 (``scripts/main.py:236-256``) as one batched ICP launch."""
+REFINE_GATES = (0.5, 0.0)   # (min_overlap, min_observability) of slamhip.plicp.apply_refinement
+
+
+def refine_edges(scanset, src, dst, tf, refine, gates=REFINE_GATES):
+    """The point-to-line refinement of the ICP edges icp(pc1 = src[b], pc2 =
+    dst[b]) -> ``tf`` (new, opt-in; ``slamhip.plicp``): ONE launch over the
+    resident ``scanset``, then ``apply_refinement`` with ``gates`` = (min_overlap,
+    min_observability).  ``refine``: the ``PlicpParams``.  Returns the transforms,
+    the mask of those that took the refinement and the ``PlicpResult``."""
+    from . import plicp as _plicp
+    if not isinstance(refine, _plicp.PlicpParams):
+        raise TypeError(f"refine must be a slamhip.plicp.PlicpParams or None, got {type(refine).__name__}")
+    src = np.asarray(src, dtype=np.int64)
+    res = _plicp.refine_batch(scanset, src, dst, tf, refine)
+    out, taken = _plicp.apply_refinement(tf, scanset.lens[src], res, gates[0], gates[1])
+    return out, taken, res
+
+
+def _edge_transforms(scanset, src, dst, tf, refine, gates):
+    """``tf`` itself without a refinement (the default), else ``refine_edges``' transforms."""
+    return tf if refine is None else refine_edges(scanset, src, dst, tf, refine, gates)[0]
+
+
+def scan_matching(odometry, lidar_points, icp_max_iters=100, icp_epsilon=0.05, scanset=None, refine=None,
+                  refine_gates=REFINE_GATES):
+    """Stage 1 (``scripts/main.py:236-256``) as one batched ICP launch.  With
+    ``refine`` a ``slamhip.plicp.PlicpParams`` (new, opt-in) every ICP edge is
+    refined with the point-to-line metric before the chain is composed; the
+    default None leaves every output as it is."""
     from . import icp as _icp
     odometry = np.asarray(odometry, dtype=np.float64)
     S = len(odometry)
@@ -62,6 +93,10 @@ def scan_matching(odometry, lidar_points, icp_max_iters=100, icp_epsilon=0.05, s
                           epsilon=icp_epsilon, max_iters=icp_max_iters)
     batch.launch()
     r = batch.result()
+    if refine is not None:
+        tf, taken, rr = refine_edges(ss, np.arange(1, S), np.arange(0, S - 1), r.tf, refine, refine_gates)
+        return ScanMatchResult(se2.compose_chain(odometry[0], tf), tf, r.err, r.iters, rr.status, rr.inliers, rr.obs,
+                               taken)
     poses = se2.compose_chain(odometry[0], r.tf)
     return ScanMatchResult(poses, r.tf, r.err, r.iters)
 
@@ -95,13 +130,18 @@ def loop_closure_inits(scanset, src, dst, init="identity", csm=None):
 
 
 def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
-                         err_thresh=LOOP_CLOSURE_ICP_ERROR, scanset=None, init="identity", csm=None):
+                         err_thresh=LOOP_CLOSURE_ICP_ERROR, scanset=None, init="identity", csm=None, refine=None,
+                         refine_gates=REFINE_GATES):
     """Stage 2, manual path (``scripts/main.py:298-307``): ICP(pc_i, pc_j,
     init = I) for every annotated pair in ONE launch; constraints are added
     in file order (``add_constraint`` overwrites a repeated (i, j) in place,
     networkx semantics), exactly as the reference's serial loop does.
     ``init="csm"`` (new, opt-in) starts every ICP from the correlative scan
     match of its pair instead of the identity (``loop_closure_inits``).
+    ``refine`` (a ``slamhip.plicp.PlicpParams``; new, opt-in): acceptance stays
+    the rule above on the point-to-point error, and an accepted constraint
+    carries the point-to-line refinement of its transform where
+    ``apply_refinement`` allows it (``refine_edges``).
     Returns the boolean mask of accepted matches."""
     from . import icp as _icp
     check_loop_closure_init(init)
@@ -114,14 +154,16 @@ def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
     batch.launch()
     r = batch.result()
     ok = r.err < err_thresh
-    for (i, j), t, good in zip(matches, r.tf, ok):
+    tfs = _edge_transforms(ss, matches[:, 0], matches[:, 1], r.tf, refine, refine_gates)
+    for (i, j), t, good in zip(matches, tfs, ok):
         if good:
             add_loop_constraint(pg, int(i), int(j), t.copy(), "icp")   # icp(pc_i, pc_j): X_i = X_j T
     return ok
 
 
 def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110, max_iters=100,
-                            epsilon=0.05, scanset=None, init="identity", csm=None):
+                            epsilon=0.05, scanset=None, init="identity", csm=None, refine=None,
+                            refine_gates=REFINE_GATES):
     """Stage 2 without annotations: the reference's ``detect_proximity``
     (``src/loop_closure_detection.py:11-39``) on resident data.  The candidate
     pairs come from the GPU search of ``slamhip.lcd`` (the nearest pose at
@@ -131,8 +173,9 @@ def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1,
     reference's greedy pass is replayed on the results: reverse order, each
     node used once, ``error < err_thresh``, the constraint in the "relative"
     convention.  ``init="csm"`` starts every ICP from the correlative scan
-    match of its pair.  Returns the candidates, a list of (i, j) in the order
-    the pass visits them, and the boolean mask of those accepted."""
+    match of its pair.  ``refine``: as in ``manual_loop_closures``.  Returns the
+    candidates, a list of (i, j) in the order the pass visits them, and the
+    boolean mask of those accepted."""
     from . import icp as _icp
     from . import lcd as _lcd
     check_loop_closure_init(init)
@@ -147,12 +190,13 @@ def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1,
                           max_iters=max_iters)
     batch.launch()
     r = batch.result()
+    tfs = _edge_transforms(ss, src, dst, r.tf, refine, refine_gates)
     used = set()
     for b, (i, j) in enumerate(cand):
         if i in used or j in used:
             continue
         if float(r.err[b]) < err_thresh:
-            add_loop_constraint(pg, i, j, r.tf[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
+            add_loop_constraint(pg, i, j, tfs[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
             used.update((i, j))
             accepted[b] = True
     return cand, accepted
@@ -162,7 +206,8 @@ SIGNATURE_LOOP_CLOSURE_INITS = LOOP_CLOSURE_INITS + ("signature",)
 
 
 def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1, 4), err_thresh=110, max_iters=100,
-                            epsilon=0.05, scanset=None, init="signature", csm=None, params=None):
+                            epsilon=0.05, scanset=None, init="signature", csm=None, params=None, refine=None,
+                            refine_gates=REFINE_GATES):
     """Stage 2 from the scans alone (new; the reference has no counterpart):
     the shape of ``proximity_loop_closures`` with the candidates of
     ``slamhip.sig`` — for every scan i the scan j, at least
@@ -175,7 +220,8 @@ def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1
     every ICP from the pure rotation by -2 pi k_ij / S of the best shift;
     ``"identity"`` and ``"csm"`` as elsewhere.  ``params``: the
     ``slamhip.sig.SigParams``.  For revisits in the direction of travel (at any
-    rotation of the scan frame): see ``slamhip.sig``.  Returns the candidates, a
+    rotation of the scan frame): see ``slamhip.sig``.  ``refine``: as in
+    ``manual_loop_closures``.  Returns the candidates, a
     list of (i, j, k) in the order the pass visits them, and the boolean mask
     of those accepted."""
     from . import icp as _icp
@@ -195,21 +241,24 @@ def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1
     batch = _icp.IcpBatch(ss, src, dst, inits, epsilon=epsilon, max_iters=max_iters)
     batch.launch()
     r = batch.result()
+    tfs = _edge_transforms(ss, src, dst, r.tf, refine, refine_gates)
     used = set()
     for b, (i, j, _) in enumerate(cand):
         if i in used or j in used:
             continue
         if float(r.err[b]) < err_thresh:
-            add_loop_constraint(pg, i, j, r.tf[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
+            add_loop_constraint(pg, i, j, tfs[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
             used.update((i, j))
             accepted[b] = True
     return cand, accepted
 
 
 def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path=5, image_err_thresh=125,
-                n_matches=10, icp_err_thresh=30, metric="hamming", scanset=None, init="identity", csm=None):
+                n_matches=10, icp_err_thresh=30, metric="hamming", scanset=None, init="identity", csm=None,
+                refine=None, refine_gates=REFINE_GATES):
     """``image_loop_closures`` with everything it computed: ``(good, accepted,
-    dist_mat, icp_result)`` (``icp_result`` None without a selected pair)."""
+    dist_mat, icp_result)`` (``icp_result`` None without a selected pair; it is
+    the point-to-point result with ``refine`` too)."""
     from . import desc as _desc
     from . import icp as _icp
     check_loop_closure_init(init)
@@ -230,7 +279,8 @@ def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path
     batch.launch()
     r = batch.result()
     accepted[:] = r.err < icp_err_thresh
-    for (i, j), t, ok in zip(pairs, r.tf, accepted):
+    tfs = _edge_transforms(ss, src, dst, r.tf, refine, refine_gates)
+    for (i, j), t, ok in zip(pairs, tfs, accepted):
         if ok:
             add_loop_constraint(pg, int(i), int(j), t.copy(), "icp")   # icp(pc_i, pc_j): X_i = X_j T
     return good, accepted, dist_mat, r
@@ -238,7 +288,8 @@ def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path
 
 def image_loop_closures(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path=5,
                         image_err_thresh=125, n_matches=10, icp_err_thresh=30,
-                        metric="hamming", scanset=None, init="identity", csm=None):
+                        metric="hamming", scanset=None, init="identity", csm=None, refine=None,
+                        refine_gates=REFINE_GATES):
     """Stage 2 from image descriptors: the reference's
     ``detect_images_direct_similarity`` (``src/loop_closure_detection.py:84-159``)
     after the keypoints.  ``descriptors``: one (n, 32) uint8 array per image
@@ -249,10 +300,10 @@ def image_loop_closures(pg, lidar_points, descriptors, image_rate=1, min_dist_al
     the exact search its default approximates), the column rule (:126-131),
     icp(pc_i, pc_j) of every selected pair in ONE launch over the resident
     ``scanset``, and the constraint where ``err < icp_err_thresh``, in the "icp"
-    convention.  Returns the selected (i, j) image pairs and the boolean mask of
-    those accepted."""
+    convention.  ``refine``: as in ``manual_loop_closures``.  Returns the selected
+    (i, j) image pairs and the boolean mask of those accepted."""
     return image_stage(pg, lidar_points, descriptors, image_rate, min_dist_along_path, image_err_thresh, n_matches,
-                       icp_err_thresh, metric, scanset, init, csm)[:2]
+                       icp_err_thresh, metric, scanset, init, csm, refine, refine_gates)[:2]
 
 
 def add_loop_constraint(pg, i, j, T, convention):

@@ -85,3 +85,23 @@ def icp_batch(pc1_list, pc2_list, init_transforms, epsilon=0.01, max_iters=100, 
     if history:
         return res.tf, res.err, res.iters, [list(h) for h in res.hist]
     return res.tf, res.err, res.iters
+
+
+def refine_point_to_line(pc1, pc2, transform, **params):
+    """New here (the reference has no counterpart): the point-to-line refinement
+    of ``transform``, a finished ``icp(pc1, pc2)`` result, on the GPU
+    (``slamhip.plicp``).  ``params``: the fields of ``slamhip.plicp.PlicpParams``
+    (``max_dist``, ``min_inliers``, ``max_iters``, ``eps_t``, ``eps_r``, ...).
+
+    Returns (3x3 transform, info): the refined transform when the refinement
+    ended CONVERGED or MAX_ITERS, otherwise ``transform``'s own values; ``info``
+    has ``status`` (its name), ``iters``, ``inliers``, ``err`` and ``obs`` of
+    the last linearisation.
+    """
+    from slamhip import plicp
+    res = plicp.refine_batch(_k.ScanSet([pc1, pc2]), [0], [1], np.asarray(transform, dtype=np.float64)[None],
+                             plicp.PlicpParams(**params))
+    status = int(res.status[0])
+    info = {"status": plicp.STATUS_NAMES[status], "iters": int(res.iters[0]), "inliers": int(res.inliers[0]),
+            "err": np.float64(res.err[0]), "obs": np.float64(res.obs[0])}
+    return res.tf[0].copy(), info

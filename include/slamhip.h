@@ -543,6 +543,101 @@ int slam_pcm_status(void* stream);
  * (four instantiations of one kernel).  Per host thread; identical results. */
 int slam_pcm_set_peel_slots(int slots);
 
+/* ---- point-to-line refinement of ICP edges (csrc/plicp_kernels.hip) -----------
+ * Refines a scan pair's transform with a gated point-to-line metric
+ * (Gauss-Newton on the distance to the matched point's tangent line), which
+ * does not pull along the walls as the point-to-point metric of
+ * slam_icp_batch_f64 does.  The reference has no counterpart; new since ABI
+ * 107.  Scans are the packed layout of slam_icp_batch_f64: pts float64[P][2]
+ * (16-byte aligned), scan_off int64[S + 1], the points of a scan in beam order.
+ * All arithmetic is fp64 and every product and sum below is rounded on its own
+ * (no FMA contraction), written with its parentheses; coordinates are finite.
+ *
+ * Normals, once per scan.  K neighbours per side (>= 1), rho2 the squared
+ * support radius (the caller's rho * rho), ctol the corner tolerance.  For
+ * point j of a scan of n points Q[0..n), with d2(a, b) = ((Qa.x - Qb.x)^2) +
+ * ((Qa.y - Qb.y)^2):
+ *   support  l = j; while l > 0, j - l < K and d2(l - 1, j) <= rho2: --l.
+ *            r = j; while r < n - 1, r - j < K and d2(r + 1, j) <= rho2: ++r.
+ *            r - l < 2: no normal.
+ *   tangent  t = Q[r] - Q[l], L2 = (t.x t.x) + (t.y t.y); L2 not > 0 or not
+ *            finite: no normal.  L = sqrt(L2), n = (-t.y / L, t.x / L) (IEEE
+ *            square root and division).
+ *   corner   off = (n.x (Qj.x - Ql.x)) + (n.y (Qj.y - Ql.y)); |off| > ctol: no
+ *            normal.
+ *   out_normals  float64[P][2], (0, 0) for none; 16-byte aligned.  Points that
+ *            belong to no scan get (0, 0) too (the array is zeroed first).
+ * A scan whose offsets descend or leave [0, P] gets no normals and raises a
+ * flag (slam_plicp_status).  SLAM_EINVAL for a null array, S < 0, P < 0,
+ * K < 1, a negative or non-finite rho2 or ctol or a misaligned array; S == 0
+ * succeeds without a launch. */
+int slam_plicp_normals_f64(const double* pts, const int64_t* scan_off, int32_t S, int64_t P, int32_t K, double rho2,
+                           double ctol, double* out_normals, void* stream);
+/* Refinement of B pairs, one workgroup per pair, every iteration on chip.
+ *   src_scan, dst_scan  int32[B]  scan indices, as slam_icp_batch_f64
+ *   init       float64[B][9]  T maps source points into the destination
+ *              frame; its bottom row is taken as 0 0 1
+ *   normals    float64[P][2]  slam_plicp_normals_f64's output for these scans
+ *   max_dist2  the squared correspondence gate; min_inliers; max_iters >= 1;
+ *   eps_t, eps_r  the stopping steps; pivot_tol (1e-9 is the usual value)
+ *   max_n1     an upper bound of the source scans' sizes, <= 8,192
+ * Per iteration, from T:
+ *   transform  x' = ((T00 x) + (T01 y)) + T02, y' = ((T10 x) + (T11 y)) + T12
+ *   match      j* the smallest j that minimises ((x' - qx)^2) + ((y' - qy)^2)
+ *              over the destination scan
+ *   gate       the point is an inlier iff that minimum is <= max_dist2; m
+ *              inliers
+ *   rows       ex = x' - qx, ey = y' - qy.  An inlier whose match has a normal
+ *              (nx, ny): a = (nx, ny, (ny x') - (nx y')), r = (nx ex) + (ny ey).
+ *              One whose match has none, two rows (the point-to-point
+ *              fallback): a = (1, 0, -y'), r = ex and a = (0, 1, x'), r = ey.
+ *   sums       H = sum a a^T (six sums), g = sum a r, e = sum r r over all
+ *              rows, in the implementation's own order: fixed (no
+ *              floating-point atomics), so a pair gives the same bits in any
+ *              batch, at any slot
+ *   err = e / m;  h = (H00 + H11) / 2, q = sqrt(max((h h) - ((H00 H11) - (H01
+ *              H01)), 0)), obs = (h - q) / (h + q): near 0 in a corridor, near
+ *              1 in a room
+ *   too few    m < min_inliers: stop, status TOO_FEW, T unchanged
+ *   solve      H delta = -g by LDL^T in the order (x, y, theta): d0 = H00, l10 =
+ *              H01 / d0, l20 = H02 / d0, d1 = H11 - (l10 H01), u = H12 - (l20
+ *              H01), l21 = u / d1, d2 = (H22 - (l20 H02)) - (l21 u); z0 = -g0,
+ *              z1 = -g1 - (l10 z0), z2 = (-g2 - (l20 z0)) - (l21 z1); dth = z2 /
+ *              d2, dy = (z1 / d1) - (l21 dth), dx = ((z0 / d0) - (l10 dy)) - (l20
+ *              dth).  A pivot d_k that is not finite or <= pivot_tol H_kk: stop,
+ *              status DEGENERATE, T unchanged
+ *   update     c = cos dth, s = sin dth, T <- [[c, -s, dx], [s, c, dy], [0, 0,
+ *              1]] T with plain products and sums: T00 = (c T00) - (s T10), T02
+ *              = ((c T02) - (s T12)) + dx, T10 = (s T00) + (c T10), T12 = ((s
+ *              T02) + (c T12)) + dy, the middle column like the first; ++it
+ *   stop       |dx| < eps_t, |dy| < eps_t and |dth| < eps_r: CONVERGED;
+ *              otherwise it == max_iters: MAX_ITERS (its transform is usable)
+ * Outputs per pair: out_tf[9]; out_iters; out_status 0 CONVERGED, 1
+ * MAX_ITERS, 2 DEGENERATE, 3 TOO_FEW; out_err, out_obs and out_inliers are
+ * those of the LAST LINEARISATION, that is of the transform before the final
+ * step (for TOO_FEW and DEGENERATE: of the linearisation that stopped; err is
+ * NaN when it had no inlier).  out_match int32[B][match_stride], NULL allowed:
+ * j* of the last linearisation per source point, -1 for an outlier and past
+ * the scan's end; match_stride >= max_n1.
+ * What only the device can see is checked there, pair by pair: a pair that
+ * names a scan outside [0, S), whose offsets descend or leave [0, P], or whose
+ * source scan exceeds max_n1 is not computed (out_status -1, out_tf = init,
+ * err and obs NaN, match -1) and raises a flag.  slam_plicp_status
+ * synchronises `stream`, reports the flags of every launch of both entry
+ * points since the previous call (SLAM_OK or SLAM_EINVAL) and clears them.
+ * Stream-ordered, graph-capturable, no host copies, nothing allocated.
+ * SLAM_EINVAL for a null array (other than out_match), B < 0, max_iters < 1,
+ * a negative or non-finite max_dist2, eps_t, eps_r or pivot_tol, a stride
+ * below max_n1 or a misaligned array; SLAM_ETOOBIG for max_n1 > 8,192 (the
+ * limit of slam_icp_batch_f64); B == 0 succeeds without a launch. */
+int slam_plicp_batch_f64(const double* pts, const int64_t* scan_off, int32_t S, int64_t P, const double* normals,
+                         const int32_t* src_scan, const int32_t* dst_scan, const double* init, int32_t B,
+                         double max_dist2, int32_t min_inliers, int32_t max_iters, double eps_t, double eps_r,
+                         double pivot_tol, int32_t max_n1, double* out_tf, double* out_err, double* out_obs,
+                         int32_t* out_inliers, int32_t* out_iters, int32_t* out_status, int32_t* out_match,
+                         int32_t match_stride, void* stream);
+int slam_plicp_status(void* stream);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
