@@ -46,6 +46,14 @@ each other at the end of the stage and removes those outside the pairwise
 consistent set (slamhip.pcm); ``--consistency-trans-tol``,
 ``--consistency-rot-tol``, ``--consistency-trans-drift`` and
 ``--consistency-rot-drift`` are its tolerances.
+``--edge-check visibility`` (new, opt-in) verifies every ICP edge on its own by
+scan visibility (slamhip.vis): a scan-matching edge that fails is re-matched
+from its odometry init (``--scan-matching-repair refine-from-init``, the
+default, or ``none`` to flag only), and a loop closure below its error
+threshold is added only if it passes too; ``--edge-check-margin``,
+``--edge-check-sectors``, ``--edge-check-max-conflict`` and
+``--edge-check-min-agree`` feed it, and the printed summary counts the edges
+flagged, repaired and rejected.
 Out of scope here (flags accepted, ignored): ORB keypoint extraction from
 images (OpenCV) and the matplotlib figures.
 
@@ -122,6 +130,19 @@ def parse(argv=None):
                    help="refinement: an edge keeps its point-to-point transform below this share of inliers")
     p.add_argument("--refine-min-observability", default=0.0, type=float,
                    help="refinement: ... and below this observability of the translation (0: off)")
+    p.add_argument("--edge-check", default="none", choices=["none", "visibility"],
+                   help="verify every ICP edge (scan matching and loop closures below their error threshold) by scan "
+                        "visibility (slamhip.vis; new, opt-in; default: none)")
+    p.add_argument("--edge-check-margin", default=0.15, type=float,
+                   help="edge check: a range within this of the other scan's agrees, one shorter by more conflicts (m)")
+    p.add_argument("--edge-check-sectors", default=360, type=int, help="edge check: bearings of a scan's range table")
+    p.add_argument("--edge-check-max-conflict", default=0.02, type=float,
+                   help="edge check: largest share of conflicting points among those that agree or conflict")
+    p.add_argument("--edge-check-min-agree", default=0.25, type=float,
+                   help="edge check: least share of a scan's points that agree")
+    p.add_argument("--scan-matching-repair", default="refine-from-init", choices=["none", "refine-from-init"],
+                   help="edge check: re-match a failing scan-matching edge from its odometry init with the gated "
+                        "point-to-line metric (default), or only flag it")
     p.add_argument("--descriptors", help="descriptors: an .npz with desc (D, 32) uint8 and off (M + 1) int64, or "
                                          "'auto' for a synthetic loop dataset")
     p.add_argument("--descriptor-metric", default="hamming", choices=["hamming", "l2"],
@@ -175,6 +196,10 @@ def parse(argv=None):
     if not (np.isfinite(a.refine_max_dist) and a.refine_max_dist >= 0 and 0 <= a.refine_min_overlap <= 1
             and 0 <= a.refine_min_observability <= 1):
         p.error("--refine-max-dist >= 0 and --refine-min-overlap, --refine-min-observability in [0, 1] expected")
+    try:
+        edge_check_params(a)
+    except ValueError as e:
+        p.error(f"--edge-check-*: {e}")
     if not (8 <= a.signature_sectors <= 128 and a.signature_sectors % 8 == 0 and a.signature_ring_width > 0):
         p.error("--signature-sectors a multiple of 8 in 8..128 and --signature-ring-width > 0 expected")
     if not (a.csm_window_m >= 0 and 0 < a.csm_angle_step_deg and 0 <= a.csm_angle_window_deg <= 180):
@@ -198,6 +223,25 @@ def refine_params(a):
     from slamhip.plicp import PlicpParams
     return {"refine": PlicpParams(max_dist=a.refine_max_dist),
             "refine_gates": (a.refine_min_overlap, a.refine_min_observability)}
+
+
+def edge_check_params(a):
+    """The VisParams of the --edge-check-* flags as the ``verify`` keyword of the
+    pipeline's stages; empty without a check."""
+    from slamhip.vis import VisParams
+    params = VisParams(sectors=a.edge_check_sectors, margin=a.edge_check_margin, min_agree=a.edge_check_min_agree,
+                       max_conflict=a.edge_check_max_conflict)
+    return {} if a.edge_check == "none" else {"verify": params}
+
+
+def closure_check(stage_out, report_entry, a):
+    """Splits a loop-closure stage's return value into its usual values and,
+    with --edge-check, the check's counts for the printed summary."""
+    if a.edge_check == "none":
+        return stage_out
+    *usual, check = stage_out
+    report_entry["edge_check"] = {"method": a.edge_check, "checked": check.checked, "rejected": check.rejected}
+    return usual[0] if len(usual) == 1 else tuple(usual)
 
 
 def csm_params(a):
@@ -275,7 +319,8 @@ def run(a):
             pg = pose_graph.PoseGraph(odometry.copy())
             stem = "odometry_pose_graph"
         else:
-            r = pipeline.scan_matching(odometry, scans, a.icp_max_iters, a.icp_epsilon, **refine_params(a))
+            r = pipeline.scan_matching(odometry, scans, a.icp_max_iters, a.icp_epsilon, **refine_params(a),
+                                       **edge_check_params(a), repair=a.scan_matching_repair)
             pg = pose_graph.PoseGraph(r.poses)
             stem = "icp_pose_graph"
             report["icp_mean_iters"] = float(np.mean(r.iters)) if len(r.iters) else 0.0
@@ -283,6 +328,11 @@ def run(a):
                 report["icp_refine"] = {"method": a.icp_refine, "edges": int(len(r.refine_status)),
                                         "taken": int(r.refine_taken.sum()),
                                         "status": np.bincount(r.refine_status, minlength=4).tolist()}
+            if r.verify_ok is not None:
+                report["edge_check"] = {"method": a.edge_check, "edges": int(len(r.verify_ok)),
+                                        "flagged": int((~r.verify_ok).sum()), "repair": a.scan_matching_repair,
+                                        "repaired": int(r.repaired.sum()),
+                                        "repair_source": np.bincount(r.repair_source, minlength=3).tolist()}
         report["scan_matching_s"] = round(time.perf_counter() - t0, 3)
         if not a.skip_icp:
             save_map(a, pg.poses, scans, "icp", report)
@@ -297,35 +347,41 @@ def run(a):
     if a.program_start in ("scan_matching", "loop_closure"):
         if a.manual_loop_closures is None and a.loop_closure_detection == "proximity":
             t0 = time.perf_counter()
-            cand, ok = pipeline.proximity_loop_closures(
+            extra = {}
+            cand, ok = closure_check(pipeline.proximity_loop_closures(
                 pg, scans, a.proximity_min_dist_along_path, a.proximity_max_dist, a.proximity_icp_error,
                 init=a.loop_closure_init, csm=csm_params(a) if a.loop_closure_init == "csm" else None,
-                **refine_params(a))
+                **refine_params(a), **edge_check_params(a)), extra, a)
             report["loop_closure_detection"] = {"method": "proximity", "candidates": len(cand),
                                                 "accepted": int(ok.sum()), "init": a.loop_closure_init,
-                                                "s": round(time.perf_counter() - t0, 3)}
+                                                "s": round(time.perf_counter() - t0, 3), **extra}
         elif a.manual_loop_closures is None and a.loop_closure_detection == "descriptors":
             ip = image_params(a)
             descriptors = load_descriptors(a, len(scans), ip["image_downsample"])
             t0 = time.perf_counter()
-            good, ok = pipeline.image_loop_closures(
+            extra = {}
+            good, ok = closure_check(pipeline.image_loop_closures(
                 pg, scans, descriptors, ip["image_downsample"],
                 ip["min_dist_along_path"], ip["image_match_error"], ip["keypoint_n_matches"],
                 a.loop_closure_icp_error, metric=a.descriptor_metric, init=a.loop_closure_init,
-                csm=csm_params(a) if a.loop_closure_init == "csm" else None, **refine_params(a))
+                csm=csm_params(a) if a.loop_closure_init == "csm" else None, **refine_params(a),
+                **edge_check_params(a)), extra, a)
             report["loop_closure_detection"] = {"method": "descriptors", "metric": a.descriptor_metric,
                                                 "selected": len(good), "accepted": int(ok.sum()),
-                                                "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
+                                                "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3),
+                                                **extra}
         elif a.manual_loop_closures is None and a.loop_closure_detection == "signatures":
             from slamhip.sig import SigParams
             t0 = time.perf_counter()
-            cand, ok = pipeline.signature_loop_closures(
+            extra = {}
+            cand, ok = closure_check(pipeline.signature_loop_closures(
                 pg, scans, a.signature_min_dist_along_path, a.signature_max_frac, a.signature_icp_error,
                 init=a.signature_init, csm=csm_params(a) if a.signature_init == "csm" else None,
-                params=SigParams(sectors=a.signature_sectors, dr=a.signature_ring_width), **refine_params(a))
+                params=SigParams(sectors=a.signature_sectors, dr=a.signature_ring_width), **refine_params(a),
+                **edge_check_params(a)), extra, a)
             report["loop_closure_detection"] = {"method": "signatures", "candidates": len(cand),
                                                 "accepted": int(ok.sum()), "init": a.signature_init,
-                                                "s": round(time.perf_counter() - t0, 3)}
+                                                "s": round(time.perf_counter() - t0, 3), **extra}
         elif a.manual_loop_closures is None:
             print("image-based loop closure detection from images needs OpenCV (out of scope; see "
                   "--loop-closure-detection descriptors); no loop closures added",
@@ -339,11 +395,13 @@ def run(a):
             else:
                 matches = pipeline.read_manual_loop_closures(a.manual_loop_closures)
             t0 = time.perf_counter()
-            ok = pipeline.manual_loop_closures(pg, scans, matches, init=a.loop_closure_init,
-                                               csm=csm_params(a) if a.loop_closure_init == "csm" else None,
-                                               **refine_params(a))
+            extra = {}
+            ok = closure_check(pipeline.manual_loop_closures(
+                pg, scans, matches, init=a.loop_closure_init,
+                csm=csm_params(a) if a.loop_closure_init == "csm" else None, **refine_params(a),
+                **edge_check_params(a)), extra, a)
             report["loop_closures"] = {"annotated": int(len(matches)), "accepted": int(ok.sum()),
-                                       "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3)}
+                                       "init": a.loop_closure_init, "s": round(time.perf_counter() - t0, 3), **extra}
         if a.loop_closure_consistency:
             t0 = time.perf_counter()
             edges, keep, unverified, res = pipeline.verify_loop_closures(pg, consistency_params(a), details=True)

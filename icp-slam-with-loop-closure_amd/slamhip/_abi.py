@@ -100,6 +100,10 @@ SIGNATURES = {
                                      c_int, c_dbl, c_dbl, c_dbl, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
                                      c_ptr, c_int, c_ptr]),
     "slam_plicp_status": (c_int, [c_ptr]),
+    "slam_vis_tables_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_int, c_ptr, c_ptr]),
+    "slam_vis_check_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_dbl,
+                                   c_int, c_ptr, c_ptr]),
+    "slam_vis_status": (c_int, [c_ptr]),
     "slam_gn_bcr_block_rows": (c_int, [c_int, c_int]),
     "slam_gn_iteration_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

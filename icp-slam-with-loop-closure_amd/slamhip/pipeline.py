@@ -17,7 +17,11 @@ The reference runs its hot path from ``scripts/main.py``:
   candidates from the scans' own rotation-invariant signatures
   (``signature_loop_closures``, ``slamhip.sig``); then, opt-in and without a
   counterpart either, the closures checked against each other and the
-  inconsistent ones removed (``verify_loop_closures``, ``slamhip.pcm``);
+  inconsistent ones removed (``verify_loop_closures``, ``slamhip.pcm``); and,
+  opt-in in stage 1 and in every loop-closure stage, each edge judged on its
+  own by scan visibility (``verify=``, ``slamhip.vis``): a stage-1 edge that
+  fails is re-matched from its odometry init (``repair_edges``), a closure that
+  fails is not added;
 * stage 3, optimisation (``scripts/main.py:322-334``): ``optimization_max_iters``
   SGD steps with learning rate 1/(k+1), then the orientation recompute.
 
@@ -48,6 +52,10 @@ class ScanMatchResult:
     refine_inliers: np.ndarray = None   # (S-1,) its inliers
     refine_obs: np.ndarray = None       # (S-1,) its observability
     refine_taken: np.ndarray = None     # (S-1,) bool: the edges whose transform is the refined one
+    verify_ok: np.ndarray = None        # (S-1,) bool: the ICP edges that pass the visibility check (verify=...)
+    verify_counts: np.ndarray = None    # (S-1, 6) its counts of the ICP edges (slamhip.vis)
+    repaired: np.ndarray = None         # (S-1,) bool: the edges whose transform is not the ICP result's
+    repair_source: np.ndarray = None    # (S-1,) 0 the ICP result, 1 refined from the odometry init, 2 the init itself
 
 
 REFINE_GATES = (0.5, 0.0)   # (min_overlap, min_observability) of slamhip.plicp.apply_refinement
@@ -73,13 +81,96 @@ def _edge_transforms(scanset, src, dst, tf, refine, gates):
     return tf if refine is None else refine_edges(scanset, src, dst, tf, refine, gates)[0]
 
 
+EDGE_REPAIRS = ("none", "refine-from-init")
+
+
+def _vis_params(verify):
+    from . import vis as _vis
+    if not isinstance(verify, _vis.VisParams):
+        raise TypeError(f"verify must be a slamhip.vis.VisParams or None, got {type(verify).__name__}")
+    return _vis
+
+
+def check_edges(scanset, src, dst, tf, params):
+    """The visibility check of the edges icp(pc1 = src[b], pc2 = dst[b]) ->
+    ``tf[b]`` over the resident ``scanset`` (new, opt-in; ``slamhip.vis``): ONE
+    launch.  ``params``: the ``VisParams``.  Returns the ``VisResult``."""
+    return _vis_params(params).check_batch(scanset, src, dst, tf, params)
+
+
+def choose_candidate(counts, ok, order):
+    """Which candidate transform of one edge to take.  ``counts``: (C, 6)
+    visibility counts, ``ok``: (C,) verdicts, ``order``: (C,) ranks (0 the ICP
+    result, 1 refined from the init, 2 the init).  The passing candidate of the
+    lowest rank above 0, else the smallest key ``(conflict0 + conflict1,
+    -(agree0 + agree1), order)`` of them all.  Returns its position."""
+    from . import vis as _vis
+    order = [int(o) for o in order]
+    passing = [c for c in range(len(order)) if ok[c] and order[c] > 0]
+    if passing:
+        return min(passing, key=lambda c: order[c])
+    return min(range(len(order)), key=lambda c: _vis.candidate_key(counts[c], order[c]))
+
+
+def repair_edges(scanset, src, dst, tf, inits, verify, repair="refine-from-init", repair_refine=None):
+    """Checks the edges icp(pc1 = src[b], pc2 = dst[b]) -> ``tf[b]`` that were
+    started from ``inits`` (``check_edges``) and, with ``repair`` =
+    "refine-from-init", re-matches those that fail: ONE
+    ``slamhip.plicp.refine_batch`` launch of the gated point-to-line metric from
+    their inits (``repair_refine``: its ``PlicpParams``, None for the defaults),
+    ONE check of the two candidates per failing edge — the refined transform
+    where its status is CONVERGED or MAX_ITERS, then the init itself — and
+    ``choose_candidate``.  A passing edge keeps its row bit for bit; "none" only
+    flags.  Returns (transforms, the ``VisResult`` of ``tf``, source (B,) int64:
+    0 ``tf``'s row, 1 refined from the init, 2 the init)."""
+    _vis = _vis_params(verify)
+    if repair not in EDGE_REPAIRS:
+        raise ValueError(f"unknown repair {repair!r} ({' | '.join(EDGE_REPAIRS)})")
+    src = np.asarray(src, dtype=np.int64)
+    dst = np.asarray(dst, dtype=np.int64)
+    tf = np.asarray(tf, dtype=np.float64).reshape(-1, 3, 3)
+    first = _vis.check_batch(scanset, src, dst, tf, verify)
+    out = tf.copy()
+    source = np.zeros(len(tf), dtype=np.int64)
+    bad = np.nonzero(~first.ok)[0]
+    if repair == "none" or len(bad) == 0:
+        return out, first, source
+    from . import plicp as _plicp
+    rp = repair_refine if repair_refine is not None else _plicp.PlicpParams()
+    if not isinstance(rp, _plicp.PlicpParams):
+        raise TypeError(f"repair_refine must be a slamhip.plicp.PlicpParams or None, got {type(rp).__name__}")
+    start = np.ascontiguousarray(np.asarray(inits, dtype=np.float64).reshape(-1, 3, 3)[bad])
+    rr = _plicp.refine_batch(scanset, src[bad], dst[bad], start, rp)
+    usable = (rr.status == _plicp.CONVERGED) | (rr.status == _plicp.MAX_ITERS)
+    nb = len(bad)
+    second = _vis.check_batch(scanset, np.concatenate([src[bad], src[bad]]), np.concatenate([dst[bad], dst[bad]]),
+                              np.concatenate([rr.tf, start]), verify)
+    for e, b in enumerate(bad):
+        cand = [(0, tf[b], first.counts[b], first.ok[b])]
+        if usable[e]:
+            cand.append((1, rr.tf[e], second.counts[e], second.ok[e]))
+        cand.append((2, start[e], second.counts[nb + e], second.ok[nb + e]))
+        c = choose_candidate([x[2] for x in cand], [x[3] for x in cand], [x[0] for x in cand])
+        out[b] = cand[c][1]
+        source[b] = cand[c][0]
+    return out, first, source
+
+
 def scan_matching(odometry, lidar_points, icp_max_iters=100, icp_epsilon=0.05, scanset=None, refine=None,
-                  refine_gates=REFINE_GATES):
+                  refine_gates=REFINE_GATES, verify=None, repair="refine-from-init", repair_refine=None):
     """Stage 1 (``scripts/main.py:236-256``) as one batched ICP launch.  With
     ``refine`` a ``slamhip.plicp.PlicpParams`` (new, opt-in) every ICP edge is
     refined with the point-to-line metric before the chain is composed; the
-    default None leaves every output as it is."""
+    default None leaves every output as it is.  With ``verify`` a
+    ``slamhip.vis.VisParams`` (new, opt-in) every ICP edge is checked by scan
+    visibility first and a failing one is re-matched from its odometry init
+    (``repair_edges``; ``repair="none"`` only flags); ``refine`` then runs on
+    the repaired transforms.  ``verify=None`` leaves every output as it is."""
     from . import icp as _icp
+    if verify is not None:
+        _vis_params(verify)
+    if repair not in EDGE_REPAIRS:
+        raise ValueError(f"unknown repair {repair!r} ({' | '.join(EDGE_REPAIRS)})")
     odometry = np.asarray(odometry, dtype=np.float64)
     S = len(odometry)
     if len(lidar_points) != S:
@@ -93,12 +184,43 @@ def scan_matching(odometry, lidar_points, icp_max_iters=100, icp_epsilon=0.05, s
                           epsilon=icp_epsilon, max_iters=icp_max_iters)
     batch.launch()
     r = batch.result()
+    tf0, checked = r.tf, {}
+    if verify is not None:
+        tf0, first, source = repair_edges(ss, np.arange(1, S), np.arange(0, S - 1), r.tf, inits, verify, repair,
+                                          repair_refine)
+        checked = dict(verify_ok=first.ok, verify_counts=first.counts, repaired=source != 0, repair_source=source)
     if refine is not None:
-        tf, taken, rr = refine_edges(ss, np.arange(1, S), np.arange(0, S - 1), r.tf, refine, refine_gates)
+        tf, taken, rr = refine_edges(ss, np.arange(1, S), np.arange(0, S - 1), tf0, refine, refine_gates)
         return ScanMatchResult(se2.compose_chain(odometry[0], tf), tf, r.err, r.iters, rr.status, rr.inliers, rr.obs,
-                               taken)
-    poses = se2.compose_chain(odometry[0], r.tf)
-    return ScanMatchResult(poses, r.tf, r.err, r.iters)
+                               taken, **checked)
+    poses = se2.compose_chain(odometry[0], tf0)
+    return ScanMatchResult(poses, tf0, r.err, r.iters, **checked)
+
+
+@dataclass
+class ClosureCheck:
+    """What a loop-closure stage's ``verify`` did (its last returned value)."""
+    checked: int           # candidates that passed the stage's error threshold and were checked
+    rejected: int          # those of them that failed the visibility check
+    ok: np.ndarray         # (B,) bool per candidate: checked and passed
+    counts: np.ndarray     # (B, 6) int64 visibility counts, 0 where the candidate was not checked
+
+
+def verify_closures(scanset, src, dst, tfs, passed, verify):
+    """The visibility check (``slamhip.vis``) of the loop-closure candidates
+    icp(pc1 = src[b], pc2 = dst[b]) -> ``tfs[b]`` that ``passed`` their stage's
+    error threshold, in ONE launch.  Returns the ``ClosureCheck``."""
+    _vis = _vis_params(verify)
+    passed = np.asarray(passed, dtype=bool)
+    idx = np.nonzero(passed)[0]
+    ok = np.zeros(len(passed), dtype=bool)
+    counts = np.zeros((len(passed), 6), dtype=np.int64)
+    if len(idx):
+        res = _vis.check_batch(scanset, np.asarray(src, dtype=np.int64)[idx], np.asarray(dst, dtype=np.int64)[idx],
+                               np.ascontiguousarray(np.asarray(tfs, dtype=np.float64)[idx]), verify)
+        ok[idx] = res.ok
+        counts[idx] = res.counts
+    return ClosureCheck(len(idx), int(len(idx) - ok.sum()), ok, counts)
 
 
 def read_manual_loop_closures(fname):
@@ -131,7 +253,7 @@ def loop_closure_inits(scanset, src, dst, init="identity", csm=None):
 
 def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
                          err_thresh=LOOP_CLOSURE_ICP_ERROR, scanset=None, init="identity", csm=None, refine=None,
-                         refine_gates=REFINE_GATES):
+                         refine_gates=REFINE_GATES, verify=None):
     """Stage 2, manual path (``scripts/main.py:298-307``): ICP(pc_i, pc_j,
     init = I) for every annotated pair in ONE launch; constraints are added
     in file order (``add_constraint`` overwrites a repeated (i, j) in place,
@@ -142,12 +264,19 @@ def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
     the rule above on the point-to-point error, and an accepted constraint
     carries the point-to-line refinement of its transform where
     ``apply_refinement`` allows it (``refine_edges``).
-    Returns the boolean mask of accepted matches."""
+    ``verify`` (a ``slamhip.vis.VisParams``; new, opt-in): a match below the
+    error threshold is added only if the transform that would be added (after
+    ``refine``) also passes the visibility check (``verify_closures``).
+    Returns the boolean mask of accepted matches; with ``verify`` the mask and
+    the ``ClosureCheck``, which says how many the check rejected."""
     from . import icp as _icp
     check_loop_closure_init(init)
+    if verify is not None:
+        _vis_params(verify)
     matches = np.asarray(matches, dtype=np.int64).reshape(-1, 2)
     if len(matches) == 0:
-        return np.zeros(0, dtype=bool)
+        none = np.zeros(0, dtype=bool)
+        return none if verify is None else (none, ClosureCheck(0, 0, none.copy(), np.zeros((0, 6), np.int64)))
     ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
     inits = loop_closure_inits(ss, matches[:, 0], matches[:, 1], init, csm)
     batch = _icp.IcpBatch(ss, matches[:, 0], matches[:, 1], inits, epsilon=epsilon, max_iters=max_iters)
@@ -155,15 +284,19 @@ def manual_loop_closures(pg, lidar_points, matches, max_iters=100, epsilon=0.05,
     r = batch.result()
     ok = r.err < err_thresh
     tfs = _edge_transforms(ss, matches[:, 0], matches[:, 1], r.tf, refine, refine_gates)
+    report = None
+    if verify is not None:
+        report = verify_closures(ss, matches[:, 0], matches[:, 1], tfs, ok, verify)
+        ok = ok & report.ok
     for (i, j), t, good in zip(matches, tfs, ok):
         if good:
             add_loop_constraint(pg, int(i), int(j), t.copy(), "icp")   # icp(pc_i, pc_j): X_i = X_j T
-    return ok
+    return ok if verify is None else (ok, report)
 
 
 def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110, max_iters=100,
                             epsilon=0.05, scanset=None, init="identity", csm=None, refine=None,
-                            refine_gates=REFINE_GATES):
+                            refine_gates=REFINE_GATES, verify=None):
     """Stage 2 without annotations: the reference's ``detect_proximity``
     (``src/loop_closure_detection.py:11-39``) on resident data.  The candidate
     pairs come from the GPU search of ``slamhip.lcd`` (the nearest pose at
@@ -173,16 +306,21 @@ def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1,
     reference's greedy pass is replayed on the results: reverse order, each
     node used once, ``error < err_thresh``, the constraint in the "relative"
     convention.  ``init="csm"`` starts every ICP from the correlative scan
-    match of its pair.  ``refine``: as in ``manual_loop_closures``.  Returns the
-    candidates, a list of (i, j) in the order the pass visits them, and the
-    boolean mask of those accepted."""
+    match of its pair.  ``refine`` and ``verify``: as in
+    ``manual_loop_closures``; the greedy pass sees only the candidates that
+    pass the check.  Returns the candidates, a list of (i, j) in the order the
+    pass visits them, and the boolean mask of those accepted; with ``verify``
+    also the ``ClosureCheck``."""
     from . import icp as _icp
     from . import lcd as _lcd
     check_loop_closure_init(init)
+    if verify is not None:
+        _vis_params(verify)
     cand = _lcd.proximity_candidates_device(pg.poses, min_dist_along_path, max_dist)
     accepted = np.zeros(len(cand), dtype=bool)
     if not cand:
-        return cand, accepted
+        return (cand, accepted) if verify is None else \
+            (cand, accepted, ClosureCheck(0, 0, accepted.copy(), np.zeros((0, 6), np.int64)))
     pairs = np.asarray(cand, dtype=np.int64)
     ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
     src, dst = pairs[:, 1], pairs[:, 0]   # icp(pc_j, pc_i), reference :33-35
@@ -191,15 +329,16 @@ def proximity_loop_closures(pg, lidar_points, min_dist_along_path=2, max_dist=1,
     batch.launch()
     r = batch.result()
     tfs = _edge_transforms(ss, src, dst, r.tf, refine, refine_gates)
+    report = None if verify is None else verify_closures(ss, src, dst, tfs, r.err < err_thresh, verify)
     used = set()
     for b, (i, j) in enumerate(cand):
         if i in used or j in used:
             continue
-        if float(r.err[b]) < err_thresh:
+        if float(r.err[b]) < err_thresh and (report is None or report.ok[b]):
             add_loop_constraint(pg, i, j, tfs[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
             used.update((i, j))
             accepted[b] = True
-    return cand, accepted
+    return (cand, accepted) if verify is None else (cand, accepted, report)
 
 
 SIGNATURE_LOOP_CLOSURE_INITS = LOOP_CLOSURE_INITS + ("signature",)
@@ -207,7 +346,7 @@ SIGNATURE_LOOP_CLOSURE_INITS = LOOP_CLOSURE_INITS + ("signature",)
 
 def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1, 4), err_thresh=110, max_iters=100,
                             epsilon=0.05, scanset=None, init="signature", csm=None, params=None, refine=None,
-                            refine_gates=REFINE_GATES):
+                            refine_gates=REFINE_GATES, verify=None):
     """Stage 2 from the scans alone (new; the reference has no counterpart):
     the shape of ``proximity_loop_closures`` with the candidates of
     ``slamhip.sig`` — for every scan i the scan j, at least
@@ -220,20 +359,23 @@ def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1
     every ICP from the pure rotation by -2 pi k_ij / S of the best shift;
     ``"identity"`` and ``"csm"`` as elsewhere.  ``params``: the
     ``slamhip.sig.SigParams``.  For revisits in the direction of travel (at any
-    rotation of the scan frame): see ``slamhip.sig``.  ``refine``: as in
-    ``manual_loop_closures``.  Returns the candidates, a
+    rotation of the scan frame): see ``slamhip.sig``.  ``refine`` and
+    ``verify``: as in ``proximity_loop_closures``.  Returns the candidates, a
     list of (i, j, k) in the order the pass visits them, and the boolean mask
-    of those accepted."""
+    of those accepted; with ``verify`` also the ``ClosureCheck``."""
     from . import icp as _icp
     from . import sig as _sig
     if init not in SIGNATURE_LOOP_CLOSURE_INITS:
         raise ValueError(f"unknown loop-closure init {init!r} ({' | '.join(SIGNATURE_LOOP_CLOSURE_INITS)})")
+    if verify is not None:
+        _vis_params(verify)
     params = params if params is not None else _sig.SigParams()
     ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
     cand = _sig.signature_candidates_device(ss, pg.poses, min_dist_along_path, params, max_frac)
     accepted = np.zeros(len(cand), dtype=bool)
     if not cand:
-        return cand, accepted
+        return (cand, accepted) if verify is None else \
+            (cand, accepted, ClosureCheck(0, 0, accepted.copy(), np.zeros((0, 6), np.int64)))
     triples = np.asarray(cand, dtype=np.int64)
     src, dst = triples[:, 1], triples[:, 0]   # icp(pc_j, pc_i), as the proximity stage
     inits = _sig.shift_inits(triples[:, 2], params.sectors) if init == "signature" else \
@@ -242,26 +384,30 @@ def signature_loop_closures(pg, lidar_points, min_dist_along_path=5, max_frac=(1
     batch.launch()
     r = batch.result()
     tfs = _edge_transforms(ss, src, dst, r.tf, refine, refine_gates)
+    report = None if verify is None else verify_closures(ss, src, dst, tfs, r.err < err_thresh, verify)
     used = set()
     for b, (i, j, _) in enumerate(cand):
         if i in used or j in used:
             continue
-        if float(r.err[b]) < err_thresh:
+        if float(r.err[b]) < err_thresh and (report is None or report.ok[b]):
             add_loop_constraint(pg, i, j, tfs[b].copy(), "relative")   # X_j = X_i T (src/pose_graph.py)
             used.update((i, j))
             accepted[b] = True
-    return cand, accepted
+    return (cand, accepted) if verify is None else (cand, accepted, report)
 
 
 def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path=5, image_err_thresh=125,
                 n_matches=10, icp_err_thresh=30, metric="hamming", scanset=None, init="identity", csm=None,
-                refine=None, refine_gates=REFINE_GATES):
+                refine=None, refine_gates=REFINE_GATES, verify=None):
     """``image_loop_closures`` with everything it computed: ``(good, accepted,
     dist_mat, icp_result)`` (``icp_result`` None without a selected pair; it is
-    the point-to-point result with ``refine`` too)."""
+    the point-to-point result with ``refine`` too); with ``verify`` also the
+    ``ClosureCheck``."""
     from . import desc as _desc
     from . import icp as _icp
     check_loop_closure_init(init)
+    if verify is not None:
+        _vis_params(verify)
     ds = descriptors if isinstance(descriptors, _desc.DescriptorSet) else _desc.DescriptorSet(descriptors)
     start = _desc.image_starts(pg.poses, min_dist_along_path, image_rate)
     if len(start) != len(ds):
@@ -271,7 +417,8 @@ def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path
     good = _desc.select_matches(dist_mat, image_err_thresh)
     accepted = np.zeros(len(good), dtype=bool)
     if not good:
-        return good, accepted, dist_mat, None
+        return (good, accepted, dist_mat, None) if verify is None else \
+            (good, accepted, dist_mat, None, ClosureCheck(0, 0, accepted.copy(), np.zeros((0, 6), np.int64)))
     pairs = np.asarray(good, dtype=np.int64) * int(image_rate)
     ss = scanset if scanset is not None else _icp.ScanSet(lidar_points)
     src, dst = pairs[:, 0], pairs[:, 1]   # icp(pc_i, pc_j), reference :136-142
@@ -280,16 +427,20 @@ def image_stage(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path
     r = batch.result()
     accepted[:] = r.err < icp_err_thresh
     tfs = _edge_transforms(ss, src, dst, r.tf, refine, refine_gates)
+    report = None
+    if verify is not None:
+        report = verify_closures(ss, src, dst, tfs, accepted, verify)
+        accepted &= report.ok
     for (i, j), t, ok in zip(pairs, tfs, accepted):
         if ok:
             add_loop_constraint(pg, int(i), int(j), t.copy(), "icp")   # icp(pc_i, pc_j): X_i = X_j T
-    return good, accepted, dist_mat, r
+    return (good, accepted, dist_mat, r) if verify is None else (good, accepted, dist_mat, r, report)
 
 
 def image_loop_closures(pg, lidar_points, descriptors, image_rate=1, min_dist_along_path=5,
                         image_err_thresh=125, n_matches=10, icp_err_thresh=30,
                         metric="hamming", scanset=None, init="identity", csm=None, refine=None,
-                        refine_gates=REFINE_GATES):
+                        refine_gates=REFINE_GATES, verify=None):
     """Stage 2 from image descriptors: the reference's
     ``detect_images_direct_similarity`` (``src/loop_closure_detection.py:84-159``)
     after the keypoints.  ``descriptors``: one (n, 32) uint8 array per image
@@ -300,10 +451,12 @@ def image_loop_closures(pg, lidar_points, descriptors, image_rate=1, min_dist_al
     the exact search its default approximates), the column rule (:126-131),
     icp(pc_i, pc_j) of every selected pair in ONE launch over the resident
     ``scanset``, and the constraint where ``err < icp_err_thresh``, in the "icp"
-    convention.  ``refine``: as in ``manual_loop_closures``.  Returns the selected
-    (i, j) image pairs and the boolean mask of those accepted."""
-    return image_stage(pg, lidar_points, descriptors, image_rate, min_dist_along_path, image_err_thresh, n_matches,
-                       icp_err_thresh, metric, scanset, init, csm, refine, refine_gates)[:2]
+    convention.  ``refine`` and ``verify``: as in ``manual_loop_closures``.
+    Returns the selected (i, j) image pairs and the boolean mask of those
+    accepted; with ``verify`` also the ``ClosureCheck``."""
+    out = image_stage(pg, lidar_points, descriptors, image_rate, min_dist_along_path, image_err_thresh, n_matches,
+                      icp_err_thresh, metric, scanset, init, csm, refine, refine_gates, verify)
+    return out[:2] if verify is None else out[:2] + out[4:]
 
 
 def add_loop_constraint(pg, i, j, T, convention):

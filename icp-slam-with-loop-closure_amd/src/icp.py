@@ -105,3 +105,22 @@ def refine_point_to_line(pc1, pc2, transform, **params):
     info = {"status": plicp.STATUS_NAMES[status], "iters": int(res.iters[0]), "inliers": int(res.inliers[0]),
             "err": np.float64(res.err[0]), "obs": np.float64(res.obs[0])}
     return res.tf[0].copy(), info
+
+
+def check_visibility(pc1, pc2, transform, **params):
+    """New here (the reference has no counterpart): is ``transform``, an
+    ``icp(pc1, pc2)`` result, believable?  Every point of one scan, mapped into
+    the other's frame, must lie on the surface that scan measured at its
+    bearing, not in front of it (``slamhip.vis``, on the GPU).  ``params``: the
+    fields of ``slamhip.vis.VisParams`` (``sectors``, ``window``, ``margin``,
+    ``min_agree``, ``max_conflict``).
+
+    Returns (verdict, info): ``info`` has the six ``counts`` (agree, conflict
+    and points of pc1 in pc2's frame, then of pc2 in pc1's) and the ``agree``
+    and ``conflict`` shares of both directions.
+    """
+    from slamhip import vis
+    res = vis.check_batch(_k.ScanSet([pc1, pc2]), [0], [1], np.asarray(transform, dtype=np.float64)[None],
+                          vis.VisParams(**params))
+    return bool(res.ok[0]), {"counts": res.counts[0].copy(), "agree": res.agree[0].copy(),
+                             "conflict": res.conflict[0].copy()}

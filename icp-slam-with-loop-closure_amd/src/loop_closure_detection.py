@@ -39,6 +39,11 @@ New function: ``detect_signatures`` proposes loop closures from the scans
 themselves (rotation-invariant signatures matched on the GPU, ``slamhip.sig``),
 needing neither nearly right poses nor a camera.
 
+New, opt-in: ``detect_proximity`` and ``detect_signatures`` take ``verify=`` (a
+``slamhip.vis.VisParams``): a candidate below its error threshold is added only
+if its transform also passes the per-edge visibility check on the GPU; they
+then return the number of candidates the check rejected.
+
 New function: ``filter_consistent`` checks the loop closures the detectors
 added against each other and removes those outside the pairwise consistent set
 (``slamhip.pcm``, on the GPU), before the optimisation sees them.
@@ -64,14 +69,20 @@ def _homog(p):
     return np.c_[p[:, :2], np.ones(len(p))]
 
 
-def _icp_pairs(pc1_list, pc2_list, init, csm):
+def _icp_pairs(pc1_list, pc2_list, init, csm, verify=None, err_thresh=None):
     """``slamhip.icp.icp_pairs`` (eps 0.05, max_iters 100) over one ScanSet
-    that the opt-in correlative scan match of the same pairs shares."""
+    that the opt-in correlative scan match of the same pairs shares.  With
+    ``verify`` (a ``slamhip.vis.VisParams``): (result, the
+    ``slamhip.pipeline.ClosureCheck`` of the pairs below ``err_thresh``)."""
     scans = [s for pair in zip(pc1_list, pc2_list) for s in pair]
     B = len(pc1_list)
     src, dst = np.arange(0, 2 * B, 2), np.arange(1, 2 * B, 2)
     ss = _k.ScanSet(scans)
-    return _k.icp_batch(ss, src, dst, loop_closure_inits(ss, src, dst, init, csm), epsilon=0.05, max_iters=100)
+    res = _k.icp_batch(ss, src, dst, loop_closure_inits(ss, src, dst, init, csm), epsilon=0.05, max_iters=100)
+    if verify is None:
+        return res
+    from slamhip.pipeline import verify_closures
+    return res, verify_closures(ss, src, dst, res.tf, res.err < err_thresh, verify)
 
 
 def _path_geometry(poses):
@@ -96,7 +107,12 @@ def proximity_candidates(poses, min_dist_along_path=2, max_dist=1):
 
 
 def detect_proximity(pose_graph, lidar_points, min_dist_along_path=2, max_dist=1, err_thresh=110,
-                     init="identity", csm=None, candidates="host"):
+                     init="identity", csm=None, candidates="host", verify=None):
+    """``verify`` (a ``slamhip.vis.VisParams``; new, opt-in, the default None is
+    the reference's behaviour): a candidate below ``err_thresh`` is added only
+    if its transform also passes the visibility check (``slamhip.vis``); the
+    greedy pass sees only those.  Returns None, or with ``verify`` the number of
+    candidates the check rejected."""
     check_loop_closure_init(init)
     if candidates == "host":
         cand = proximity_candidates(pose_graph.poses, min_dist_along_path, max_dist)
@@ -106,24 +122,28 @@ def detect_proximity(pose_graph, lidar_points, min_dist_along_path=2, max_dist=1
     else:
         raise ValueError(f"unknown candidate search {candidates!r} (host | device)")
     if not cand:
-        return
+        return None if verify is None else 0
     # icp(pc_j, pc_i) for every candidate, one launch (reference :33-35)
     res = _icp_pairs([_homog(lidar_points[j]) for _, j in cand], [_homog(lidar_points[i]) for i, _ in cand],
-                     init, csm)
+                     init, csm, verify, err_thresh)
+    report = None
+    if verify is not None:
+        res, report = res
     used = set()
     for b, (i, j) in enumerate(cand):
         if i in used or j in used:
             continue
         error = float(res.err[b])
-        if error < err_thresh:
+        if error < err_thresh and (report is None or report.ok[b]):
             print("%d %d %f" % (i, j, error))
             # icp(pc_j, pc_i): X_j = X_i T, the "relative" convention (src/pose_graph.py)
             add_loop_constraint(pose_graph, i, j, res.tf[b].copy(), "relative")
             used.update((i, j))
+    return None if report is None else report.rejected
 
 
 def detect_signatures(pose_graph, lidar_points, min_dist_along_path=5, max_frac=(1, 4), err_thresh=110,
-                      init="signature", csm=None, params=None):
+                      init="signature", csm=None, params=None, verify=None):
     """New, without a counterpart in the reference: loop closures from the scans
     alone, beside ``detect_proximity`` and with its shape.  Every scan's best
     rotation-invariant signature match at least ``min_dist_along_path`` further
@@ -131,10 +151,12 @@ def detect_signatures(pose_graph, lidar_points, min_dist_along_path=5, max_frac=
     asked for nearness), icp(pc_j, pc_i) of all of them in one launch from the
     rotation the match found, and the same greedy pass
     (``slamhip.pipeline.signature_loop_closures``).  For revisits in the
-    direction of travel, at any rotation of the scan frame."""
+    direction of travel, at any rotation of the scan frame.  ``verify``: as in
+    ``detect_proximity``."""
     from slamhip.pipeline import signature_loop_closures
-    signature_loop_closures(pose_graph, lidar_points, min_dist_along_path, max_frac, err_thresh, init=init, csm=csm,
-                            params=params)
+    out = signature_loop_closures(pose_graph, lidar_points, min_dist_along_path, max_frac, err_thresh, init=init,
+                                  csm=csm, params=params, verify=verify)
+    return None if verify is None else out[2].rejected
 
 
 def filter_consistent(pose_graph, params=None, remove=True):

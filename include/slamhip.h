@@ -638,6 +638,63 @@ int slam_plicp_batch_f64(const double* pts, const int64_t* scan_off, int32_t S, 
                          int32_t match_stride, void* stream);
 int slam_plicp_status(void* stream);
 
+/* ---- verification of an edge by scan visibility (csrc/vis_kernels.hip) ---------
+ * Says, for one edge icp(pc1 = src, pc2 = dst) -> T on its own, whether T is
+ * believable: the points of one scan, mapped into the other scan's frame, must
+ * lie on the surface that scan measured at their bearing and not in front of
+ * it, where that scan saw free space.  The reference has no counterpart; new
+ * since ABI 108.  Scans are the packed layout of slam_icp_batch_f64.  All
+ * arithmetic is fp64, every written parenthesis below is one rounding (no FMA
+ * contraction), sqrt is the IEEE square root.  The scans keep no record of
+ * beams without a return, so a direction without a point is "unknown".
+ *
+ *   dirs      float64[S][2]  sector centres (cos, sin)((k + 0.5) 2 pi / S), made
+ *             by the caller; 3 <= S <= 1024
+ *   sector    of a point (x, y): the first maximum over k = 0..S-1 of
+ *             (c_k x) + (s_k y) (a comparison with NaN is false: sector 0)
+ *   table     of a scan: R2[k] = the minimum of r2 = (x x) + (y y) over the
+ *             scan's points in sector k; +inf for an empty sector; a point
+ *             whose r2 is not finite takes no part.  A minimum of non-negative
+ *             doubles is exact and order-free.
+ * slam_vis_tables_f64 writes out_r2 float64[n_scans][S], one workgroup per
+ * scan.  A scan whose offsets descend or leave [0, P] keeps a row of +inf and
+ * raises a flag.
+ *
+ * One direction of an edge: the points p of scan A through a transform M
+ * against scan B's table, window W >= 0 (2 W + 1 <= S), margin >= 0:
+ *   q         qx = ((M00 x) + (M01 y)) + M02, qy = ((M10 x) + (M11 y)) + M12
+ *   rq = sqrt((qx qx) + (qy qy)), k the sector of q
+ *   entries   e_w = R2_B[(k + w) mod S], w = -W..W; seen iff finite, then
+ *             re_w = sqrt(e_w)
+ *   agrees    |re_w - rq| <= margin for some seen entry
+ *   conflicts it does not agree, all 2 W + 1 entries are seen and
+ *             rq + margin < min_w re_w
+ *   unknown   otherwise (rq not finite: always)
+ * An edge: direction 0 maps src's points through T (bottom row taken as 0 0 1)
+ * against dst's table; direction 1 maps dst's points against src's table
+ * through the rigid inverse, rotation the transpose of T's 2x2 block,
+ * translation (-((T00 tx) + (T10 ty)), -((T01 tx) + (T11 ty))).
+ *   out_counts int32[B][6]  (agree0, conflict0, n0, agree1, conflict1, n1), n_d
+ *             the number of points mapped in direction d
+ * Counts are integer sums of per-wave popcounts: the same for any launch
+ * shape.  An edge that names a scan outside [0, n_scans), or one whose offsets
+ * descend or leave [0, P], is not computed: its six counts are -1 and a flag
+ * is raised; the other edges of the launch are unaffected.  slam_vis_status
+ * synchronises `stream`, reports the flags of every launch of both entry
+ * points since the previous call (SLAM_OK or SLAM_EINVAL) and clears them.
+ * The verdict (which shares of agreeing and conflicting points pass) is the
+ * caller's: slamhip.vis.VisParams.passes.
+ * Stream-ordered, graph-capturable, no host copies, nothing allocated.
+ * SLAM_EINVAL, before any launch, for a null array, S outside 3..1024, W < 0
+ * or 2 W + 1 > S, a negative or non-finite margin, negative sizes or
+ * misaligned points; B == 0 and n_scans == 0 succeed without a launch. */
+int slam_vis_tables_f64(const double* pts, const int64_t* scan_off, int32_t n_scans, int64_t P, const double* dirs,
+                        int32_t S, double* out_r2, void* stream);
+int slam_vis_check_f64(const double* pts, const int64_t* scan_off, int32_t n_scans, int64_t P, const double* dirs,
+                       int32_t S, const double* tables, const int32_t* src, const int32_t* dst, const double* tf,
+                       int32_t B, double margin, int32_t W, int32_t* out_counts, void* stream);
+int slam_vis_status(void* stream);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
