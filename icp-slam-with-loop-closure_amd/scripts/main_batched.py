@@ -54,6 +54,11 @@ threshold is added only if it passes too; ``--edge-check-margin``,
 ``--edge-check-sectors``, ``--edge-check-max-conflict`` and
 ``--edge-check-min-agree`` feed it, and the printed summary counts the edges
 flagged, repaired and rejected.
+``--save-map FILE`` (new, opt-in) writes the last occupancy grid built, with its
+origin and cell width, as one ``.npz`` (slamhip.loc.save_map) that
+scripts/localize.py reads; ``--map-check`` (new, opt-in) scores every scan at
+the pose the grid was built from against that grid (slamhip.loc.score_poses)
+and writes ``<name>_map_check.npz`` into the results directory.
 Out of scope here (flags accepted, ignored): ORB keypoint extraction from
 images (OpenCV) and the matplotlib figures.
 
@@ -168,6 +173,13 @@ def parse(argv=None):
     p.add_argument("--miss-odds", default=2, type=int)
     for f in ("--produce-odometry-map", "--skip-occupancy-grid", "--save-map-files", "--occupancy-grid-mle"):
         p.add_argument(f, action="store_true")
+    p.add_argument("--save-map", metavar="FILE",
+                   help="write the last occupancy grid built, its origin and cell width as one .npz for "
+                        "scripts/localize.py (slamhip.loc; new, opt-in)")
+    p.add_argument("--map-check", action="store_true",
+                   help="score every scan at its pose against the grid built from those poses and write "
+                        "<name>_map_check.npz into the results directory (slamhip.loc.score_poses; new, opt-in)")
+    p.add_argument("--map-check-d-cap", default=20, type=int, help="map check: cap of the distance field (cells)")
     # reference flags for figures (accepted, not used here) and image matching (--loop-closure-detection descriptors)
     for f, kw in (("--figure-dpi", dict(type=int)), ("--figure-width", dict(type=float)),
                   ("--figure-height", dict(type=float)), ("--image-downsample", dict(type=int)),
@@ -179,6 +191,10 @@ def parse(argv=None):
     a = p.parse_args(argv)
     if STAGES.index(a.program_end) < STAGES.index(a.program_start):
         p.error("--program-end precedes --program-start")
+    if (a.save_map or a.map_check) and a.skip_occupancy_grid:
+        p.error("--save-map / --map-check need the occupancy grid (drop --skip-occupancy-grid)")
+    if not 1 <= a.map_check_d_cap <= 255:
+        p.error("--map-check-d-cap in 1..255 expected")
     if a.program_start != "scan_matching" and not a.pose_graph:
         p.error("starting after scan matching needs --pose-graph")
     if a.loop_closure_detection == "descriptors" and not a.descriptors:
@@ -288,6 +304,8 @@ def save_map(a, poses, scans, name, report):
     t0 = time.perf_counter()
     og, (min_x, min_y) = pog.produce_occupancy_grid(np.asarray(poses), scans, a.cell_width, kHitOdds=a.hit_odds,
                                                     kMissOdds=a.miss_odds)
+    if a.save_map or a.map_check:
+        map_outputs(a, og, (min_x, min_y), np.asarray(poses), scans, name, report)
     if a.occupancy_grid_mle:
         og = pog.grid_mle(og, unknown_empty=True)
     pog.save_image(og, os.path.join(a.results_dir, "%s_og.png" % name))
@@ -295,6 +313,23 @@ def save_map(a, poses, scans, name, report):
         pog.save_grid(og, os.path.join(a.results_dir, "%s.map" % name), a.cell_width)
     report["map_" + name] = {"cells": list(og.shape), "origin": [float(min_x), float(min_y)],
                              "s": round(time.perf_counter() - t0, 3)}
+
+
+def map_outputs(a, og, origin, poses, scans, name, report):
+    """--save-map: the grid as slamhip.loc's .npz (the last grid built wins);
+    --map-check: every scan's cost on the grid's distance field at its pose."""
+    from slamhip import loc
+    if a.save_map:
+        loc.save_map(a.save_map, og, origin, a.cell_width)
+    if a.map_check:
+        t0 = time.perf_counter()
+        field = loc.LikelihoodField(og, origin, a.cell_width, d_cap=a.map_check_d_cap)
+        cost, mean = loc.score_poses(field, scans, poses)
+        np.savez(os.path.join(a.results_dir, "%s_map_check.npz" % name), cost=cost, mean=mean, poses=poses,
+                 d_cap=np.int64(a.map_check_d_cap))
+        report["map_check_" + name] = {"scans": int(len(cost)), "mean_sq_cells": float(np.mean(mean)),
+                                       "worst_scan": int(np.argmax(mean)), "worst_sq_cells": float(np.max(mean)),
+                                       "s": round(time.perf_counter() - t0, 3)}
 
 
 def run(a):

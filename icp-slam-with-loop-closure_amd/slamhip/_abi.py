@@ -104,6 +104,16 @@ SIGNATURES = {
     "slam_vis_check_f64": (c_int, [c_ptr, c_ptr, c_int, c_i64, c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_dbl,
                                    c_int, c_ptr, c_ptr]),
     "slam_vis_status": (c_int, [c_ptr]),
+    "slam_loc_field_work_size": (c_i64, [c_int, c_int]),
+    "slam_loc_field": (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "slam_loc_search_work_size": (c_i64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "slam_loc_search": (c_int, [c_ptr, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_ptr, c_ptr, c_int, c_i64, c_ptr,
+                                c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "slam_loc_set_table": (c_int, [c_int]),
+    "slam_loc_refine_f64": (c_int, [c_ptr, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_ptr, c_ptr, c_int, c_i64, c_ptr,
+                                    c_ptr, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_ptr, c_ptr, c_ptr, c_ptr,
+                                    c_ptr, c_ptr]),
+    "slam_loc_status": (c_int, [c_ptr]),
     "slam_gn_bcr_block_rows": (c_int, [c_int, c_int]),
     "slam_gn_iteration_f64": (c_int, [c_ptr, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_ptr,
                                       c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),

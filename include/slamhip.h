@@ -695,6 +695,106 @@ int slam_vis_check_f64(const double* pts, const int64_t* scan_off, int32_t n_sca
                        int32_t B, double margin, int32_t W, int32_t* out_counts, void* stream);
 int slam_vis_status(void* stream);
 
+/* ---- localisation in a finished occupancy grid (csrc/loc_kernels.hip) ----------
+ * Where a scan lies in the map that produce_occupancy_grid made: the int8 grid
+ * (H, W), row = y, its origin (min_x, min_y) and its cell width cw.  The
+ * reference has no counterpart; new since ABI 109.  Scans are the packed layout
+ * of slam_icp_batch_f64.  tests/loc_ref.py restates all three definitions.
+ *
+ * Field.  Cell (r, c) is occupied iff grid[r][c] > occ_min (grid_mle's rule at
+ * 0); d_cap in 1..255 cells:
+ *   F[r][c] = min(d_cap^2, min over occupied (r', c') of (r - r')^2 + (c - c')^2)
+ * as uint16; d_cap^2 everywhere without an occupied cell in reach.  Integers
+ * only: exact.  work: slam_loc_field_work_size(H, W) BYTES.  SLAM_EINVAL for a
+ * null array, H or W <= 0, H > 65,535, d_cap outside 1..255, occ_min outside
+ * int8. */
+int64_t slam_loc_field_work_size(int32_t H, int32_t W);
+int slam_loc_field(const int8_t* grid, int32_t H, int32_t W, int32_t occ_min, int32_t d_cap, uint16_t* out_field,
+                   void* work, void* stream);
+/* Window search of B queries against the one field.
+ *   q_scan    int32[B]  the query's scan
+ *   centre    float64[B][3]  (theta0, x0, y0) in the map frame
+ *   rot       float64[B][n_theta][2]  (cos, sin) of theta_k = theta0 +
+ *             (k - n_theta / 2) d_theta, evaluated by the caller as for
+ *             slam_csm_batch
+ *   nx, ny, step   shift window: (i - nx / 2) step cells in x, (j - ny / 2)
+ *             step cells in y, step >= 1
+ * A point (px, py) of the scan maps to gx = (c px - s py) + x0, gy = (s px +
+ * c py) + y0 (every operation rounded on its own), its cell is cx = floor((gx -
+ * min_x) / cw), cy = floor((gy - min_y) / cw) (true fp64 division).  Cost
+ * C[k][j][i] = sum over the scan's points of F[cy + (j - ny / 2) step][cx +
+ * (i - nx / 2) step], a cell outside the grid (or beyond int32) adding d_cap^2.
+ * Only integers are summed: the result does not depend on summation order or
+ * launch shape.
+ *   max_n       the largest queried scan; max_n d_cap^2 >= 2^31 is refused
+ *   out_best    int32[B][4]  minimum cost, then k, j, i of the minimum with
+ *               the smallest flat index (k ny + j) nx + i
+ *   out_costs   int32[B][n_theta][ny][nx] the whole volume, or NULL
+ *   work        slam_loc_search_work_size(B, H, W, n_theta, ny, nx, step) BYTES
+ * The caller assembles the pose from theta_k, x0 + (i - nx / 2) step cw and
+ * y0 + (j - ny / 2) step cw.  A query that names a scan outside [0, S), one
+ * whose offsets descend or leave [0, P], or one of more than max_n points is
+ * not computed: its out_best row is -1 (its costs are not written) and a flag
+ * is raised; slam_loc_status synchronises `stream`, reports the flags of every
+ * launch of the search and the refinement since the previous call (SLAM_OK or
+ * SLAM_EINVAL) and clears them.  SLAM_EINVAL, before any launch, for a null
+ * array, B <= 0, a non-positive H, W, cw, n_theta, nx, ny or step, d_cap
+ * outside 1..255, a cost volume n_theta ny nx of 2^31 or more entries, a
+ * bordered table (H + 2 ny step) (W + 2 nx step) of 2^31 or more cells, or
+ * max_n d_cap^2 >= 2^31 (slam_loc_search_work_size returns SLAM_EINVAL for
+ * such a shape too). */
+int64_t slam_loc_search_work_size(int32_t B, int32_t H, int32_t W, int32_t n_theta, int32_t ny, int32_t nx,
+                                  int32_t step);
+int slam_loc_search(const uint16_t* field, int32_t H, int32_t W, double min_x, double min_y, double cell_width,
+                    int32_t d_cap, const double* pts, const int64_t* scan_off, int32_t S, int64_t P,
+                    const int32_t* q_scan, const double* centre, const double* rot, int32_t B, int32_t max_n,
+                    int32_t n_theta, int32_t nx, int32_t ny, int32_t step, int32_t* out_best, int32_t* out_costs,
+                    void* work, void* stream);
+/* Diagnostics: the search gathers a table of 2-byte entries (2, default) or,
+ * when d_cap <= 15, of 1-byte entries (1; DESIGN.md section 3.12 has the A/B).
+ * Per host thread; identical results. */
+int slam_loc_set_table(int width);
+/* Sub-cell refinement: Gauss-Newton on the field in metres from init[b] =
+ * (theta, x, y), one pose per query.  D[r][c] = sqrt(F[r][c]) cw (IEEE square
+ * root of the integer, one product), sampled at cell centres, bilinear between
+ * them.  Per iteration c = cos(theta), s = sin(theta) (the device's; the only
+ * values that may differ from the restatement's in the last place), and per
+ * point (every written parenthesis one rounding, no FMA contraction):
+ *   gx = ((c px) - (s py)) + x,  gy = ((s px) + (c py)) + y
+ *   u = ((gx - min_x) / cw) - 0.5,  v = ((gy - min_y) / cw) - 0.5
+ *   i0 = floor(u), j0 = floor(v), a = u - i0, b = v - j0
+ *   D00 = D[j0][i0], D10 = D[j0][i0 + 1], D01 = D[j0 + 1][i0], D11 = D[j0 + 1][i0 + 1]
+ *   r  = ((1 - b) (((1 - a) D00) + (a D10))) + (b (((1 - a) D01) + (a D11)))
+ *   jx = (((1 - b) (D10 - D00)) + (b (D11 - D01))) / cw
+ *   jy = (((1 - a) (D01 - D00)) + (a (D11 - D10))) / cw
+ *   jt = (jx ((-s px) - (c py))) + (jy ((c px) - (s py)))
+ * A point is left out when one of its four cells is outside the grid (i0 outside
+ * 0..W-2 or j0 outside 0..H-2, tested in fp64) or all four F equal d_cap^2.  The
+ * m inliers' rows J = (jx, jy, jt) give H = sum J J^T, g = sum J r, e = sum r r,
+ * plain fp64 sums in this order: thread t of the 256 adds its points t, t + 256,
+ * ... in ascending order; the 64 threads of a wave are added by common.hpp's
+ * wave_sum tree, the four waves in ascending order.  The launch shape is fixed,
+ * so the order is.  rms = sqrt(e / m).
+ *   status 3  m == 0 or m < min_inlier_frac n (n the scan's points): stop
+ *   status 2  LDL^T pivots d_k of H as in slam_plicp_batch_f64: a pivot that is
+ *             not finite or d_k <= pivot_tol H_kk: stop
+ *   otherwise (dx, dy, dth) = -H^-1 g by that factorisation; x += dx, y += dy,
+ *             theta += dth, iters += 1
+ *   status 0  sqrt((dx dx) + (dy dy)) < eps_t and |dth| < eps_r
+ *   status 1  iters == max_iters
+ * Outputs per query: out_pose (theta, x, y), out_rms and out_inliers of the last
+ * linearisation, out_iters, out_status.  A query outside its bounds (as for the
+ * search) keeps its init pose, rms NaN, status -1, and raises the flag.
+ * SLAM_EINVAL for a null array, a negative size, max_iters < 1, a negative or
+ * non-finite tolerance, min_inlier_frac above 1, a bad grid shape or d_cap;
+ * B == 0 succeeds without a launch. */
+int slam_loc_refine_f64(const uint16_t* field, int32_t H, int32_t W, double min_x, double min_y, double cell_width,
+                        int32_t d_cap, const double* pts, const int64_t* scan_off, int32_t S, int64_t P,
+                        const int32_t* q_scan, const double* init, int32_t B, int32_t max_n, int32_t max_iters,
+                        double eps_t, double eps_r, double min_inlier_frac, double pivot_tol, double* out_pose,
+                        double* out_rms, int32_t* out_inliers, int32_t* out_iters, int32_t* out_status, void* stream);
+int slam_loc_status(void* stream);
+
 /* Diagnostics (kernel-shape sweeps; not needed by callers). */
 int slam_icp_num_instances(void);
 int slam_icp_instance_shape(int i, int* block, int* qpt);
