@@ -60,14 +60,19 @@ def rotations(theta0, n_theta, d_theta):
 
 def cells(pts, c, s, x0, y0, origin, cw):
     """Integer cells (cx, cy) of a scan at one rotation and centre; clipped in
-    fp64 far outside any grid before the conversion, like the device."""
+    fp64 far outside any grid before the conversion, like the device.  A cell
+    that is not finite (a coordinate that overflowed to inf, or inf - inf = NaN)
+    is outside the map: NaN goes to the low end, as the device's fmax does."""
     px, py = pts[:, 0], pts[:, 1]
-    gx = (c * px - s * py) + x0
-    gy = (s * px + c * py) + y0
-    cx = np.floor((gx - origin[0]) / cw)
-    cy = np.floor((gy - origin[1]) / cw)
     big = 2.0 ** 40
-    return np.clip(cx, -big, big).astype(np.int64), np.clip(cy, -big, big).astype(np.int64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        gx = (c * px - s * py) + x0
+        gy = (s * px + c * py) + y0
+        cx = np.floor((gx - origin[0]) / cw)
+        cy = np.floor((gy - origin[1]) / cw)
+        cx = np.where(np.isnan(cx), -big, np.clip(cx, -big, big))
+        cy = np.where(np.isnan(cy), -big, np.clip(cy, -big, big))
+    return cx.astype(np.int64), cy.astype(np.int64)
 
 
 def search(F, origin, cw, d_cap, pts, centre, n_theta, d_theta, nx, ny, step):
@@ -134,12 +139,13 @@ def linearise(F, origin, cw, d_cap, pts, pose, rng=None):
     x, y, th = (np.float64(v) for v in pose)
     c, s = np.cos(th), np.sin(th)
     px, py = pts[:, 0], pts[:, 1]
-    gx = ((c * px) - (s * py)) + x
-    gy = ((s * px) + (c * py)) + y
-    u = ((gx - origin[0]) / cw) - 0.5
-    v = ((gy - origin[1]) / cw) - 0.5
-    fu, fv = np.floor(u), np.floor(v)
-    ok = (fu >= 0) & (fu <= W - 2) & (fv >= 0) & (fv <= Hc - 2)
+    with np.errstate(over="ignore", invalid="ignore"):   # a point that overflows is not on the field
+        gx = ((c * px) - (s * py)) + x
+        gy = ((s * px) + (c * py)) + y
+        u = ((gx - origin[0]) / cw) - 0.5
+        v = ((gy - origin[1]) / cw) - 0.5
+        fu, fv = np.floor(u), np.floor(v)
+        ok = (fu >= 0) & (fu <= W - 2) & (fv >= 0) & (fv <= Hc - 2)
     i0 = np.where(ok, fu, 0).astype(np.int64)
     j0 = np.where(ok, fv, 0).astype(np.int64)
     if W < 2 or Hc < 2:
@@ -151,7 +157,7 @@ def linearise(F, origin, cw, d_cap, pts, pose, rng=None):
         f01, f11 = F[j0 + 1, i0].astype(np.int64), F[j0 + 1, i0 + 1].astype(np.int64)
     cap2 = d_cap * d_cap
     inl = ok & ~((f00 == cap2) & (f10 == cap2) & (f01 == cap2) & (f11 == cap2))
-    a, b = (u - fu)[inl], (v - fv)[inl]
+    a, b = u[inl] - fu[inl], v[inl] - fv[inl]
     a1, b1 = 1.0 - a, 1.0 - b
     D00, D10 = np.sqrt(f00[inl].astype(np.float64)) * cw, np.sqrt(f10[inl].astype(np.float64)) * cw
     D01, D11 = np.sqrt(f01[inl].astype(np.float64)) * cw, np.sqrt(f11[inl].astype(np.float64)) * cw
