@@ -75,13 +75,34 @@ def _check_params(p):
         raise ValueError("csm: d_theta must be finite")
 
 
+def check_offsets(off, n_points, n_scans=None):
+    """Raises ValueError unless ``off`` are the offsets of ``n_scans`` packed
+    scans (any number when None) within ``n_points`` points: one-dimensional
+    integers, ``n_scans + 1`` of them, the first at least 0, non-decreasing,
+    the last at most ``n_points``.  The kernels read ``scan_off`` unchecked."""
+    off = np.asarray(off)
+    if off.ndim != 1 or len(off) < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("csm: scan offsets must be a non-empty 1-D integer array")
+    if n_scans is not None and len(off) != n_scans + 1:
+        raise ValueError(f"csm: {len(off)} scan offsets for {n_scans} scans")
+    if off[0] < 0:
+        raise ValueError(f"csm: first scan offset {int(off[0])} < 0")
+    if np.any(off[1:] < off[:-1]):
+        s = int(np.argmax(off[1:] < off[:-1]))
+        raise ValueError(f"csm: scan offsets decrease at scan {s} ({int(off[s])} > {int(off[s + 1])})")
+    if off[-1] > n_points:
+        raise ValueError(f"csm: last scan offset {int(off[-1])} exceeds the {int(n_points)} points")
+
+
 def csm_batch(scans, src, dst, centre=None, params=CsmParams(), return_scores=False, device=None, stream=None):
     """Correlative scan match of B pairs (query ``src[b]`` against reference
-    ``dst[b]``) over a list of scans or a ``slamhip.icp.ScanSet``; ``centre``
-    (B, 3) holds the search centres (theta0, tx0, ty0), zeros by default.
-    Returns a CsmResult."""
+    ``dst[b]``) over a list of scans or a ``slamhip.icp.ScanSet`` (one made by
+    ``slamhip.plicp.packed_scans`` too: its offsets are checked here, on the
+    host, and empty scans score 0 everywhere); ``centre`` (B, 3) holds the
+    search centres (theta0, tx0, ty0), zeros by default.  Returns a CsmResult."""
     _check_params(params)
     ss = scans if isinstance(scans, _icp.ScanSet) else _icp.ScanSet(scans, device)
+    check_offsets(ss.off, len(ss.host_pts), len(ss))
     if not np.all(np.isfinite(ss.host_pts)):
         raise ValueError("non-finite scan points")
     src = np.asarray(src, dtype=np.int32)
