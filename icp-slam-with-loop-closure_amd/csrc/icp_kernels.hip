@@ -3497,7 +3497,7 @@ using namespace slamhip;
 
 extern "C" {
 
-int slam_abi_version(void) { return 109; }
+int slam_abi_version(void) { return 110; }
 
 const char* slam_last_error(void) { return last_error_buf(); }
 

@@ -129,10 +129,15 @@ SIGNATURES = {
     "slam_gn_schur_supported": (c_int, []),
     "slam_gn_set_fused_wait": (c_int, [ctypes.c_uint32]),
     "slam_gn_bcr_variant": (c_int, []),
+    "slam_gn_robust_weights_f64": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_dbl, c_dbl, c_ptr,
+                                           c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 # bits of slam_gn_bcr_variant() (SLAM_GN_VARIANT_* in include/slamhip.h)
 GN_VARIANT_CHOL, GN_VARIANT_LEGACY, GN_VARIANT_ODD_MFMA, GN_VARIANT_SPLIT, GN_VARIANT_FUSED_BACK = 1, 2, 4, 8, 16
+# SLAM_LOSS_* and SLAM_GN_ROBUST_BLOCK (slam_gn_robust_weights_f64)
+LOSSES = {"huber": 0, "cauchy": 1, "gm": 2, "dcs": 3, "gnc-gm": 4}
+GN_ROBUST_BLOCK = 256
 
 
 class SlamHipError(RuntimeError):

@@ -506,12 +506,28 @@ def verify_loop_closures(pg, params=None, remove=True, details=False):
 
 
 def optimize(pg, lidar_points, optimization_max_iters=50, icp_max_iters=100, icp_epsilon=0.05,
-             icp_recompute=False, method="sgd", gn_iterations=10):
+             icp_recompute=False, method="sgd", gn_iterations=10, gn_loss=None, gn_loss_scale=1.0,
+             gn_robust_edges="loops", gn_drop_below=None, report=None):
     """Stage 3 (``scripts/main.py:322-334``): SGD steps with learning rate
     1/(k+1) on device-resident poses, then the orientation recompute; or, with
     ``method="gn"``, the Gauss-Newton solve followed by the same recompute.
-    Updates ``pg.poses`` in place."""
+    Updates ``pg.poses`` in place.
+
+    ``gn_loss`` (new, opt-in; ``method="gn"`` only) runs the robust solve
+    (``optimize_pose_graph(loss=...)``; ``gn_loss_scale`` in units of
+    sqrt(information) x metres).  With ``gn_drop_below`` = R the loop
+    closures (edges with |b - a| != 1) whose final ratio is below R are then
+    removed from the graph (``pg.remove_constraint``, as
+    ``verify_loop_closures(remove=True)`` removes edges) and the plain
+    iterations run once more on what is left; the removed (a, b) pairs go to
+    ``report["gn_dropped"]`` when a dict is given."""
     import src.pose_graph_optimization as pgo_drop_in
+    if gn_loss in (None, "none"):
+        gn_loss = None
+    if method != "gn" and (gn_loss is not None or gn_drop_below is not None):
+        raise ValueError("gn_loss / gn_drop_below need method='gn'")
+    if gn_drop_below is not None and gn_loss is None:
+        raise ValueError("gn_drop_below needs a gn_loss")
     if method == "sgd":
         from . import pgo as _pgo
         ea, eb, tf = pg.edge_arrays()
@@ -519,6 +535,18 @@ def optimize(pg, lidar_points, optimization_max_iters=50, icp_max_iters=100, icp
         for k in range(optimization_max_iters):
             solver.step(1.0 / float(k + 1))
         pg.poses[...] = solver.host_poses()
+    elif method == "gn" and gn_loss is not None:
+        _, wts = pgo_drop_in.optimize_pose_graph(pg, iterations=gn_iterations, loss=gn_loss, loss_scale=gn_loss_scale,
+                                                 robust_edges=gn_robust_edges, return_weights=True)
+        if gn_drop_below is not None:
+            loops = np.abs(wts["eb"].astype(np.int64) - wts["ea"]) != 1
+            drop = np.flatnonzero(loops & wts["robust"] & (wts["ratio"] < gn_drop_below))
+            pairs = [(int(wts["ea"][e]), int(wts["eb"][e])) for e in drop]
+            for a, b in pairs:
+                pg.remove_constraint(a, b)
+            if report is not None:
+                report["gn_dropped"] = pairs
+            pgo_drop_in.optimize_pose_graph(pg, iterations=gn_iterations)
     elif method == "gn":
         pgo_drop_in.optimize_pose_graph(pg, iterations=gn_iterations)
     else:

@@ -278,6 +278,41 @@ int slam_gn_bcr_variant(void);
  * ticks (0: the default 0.2 s); a tiny wait forces the timeout path. */
 int slam_gn_set_fused_wait(uint32_t ticks);
 
+/*
+ * Robust loss kernels for the Gauss-Newton iterations above, by per-edge
+ * reweighting (new since ABI 110).  One launch, one
+ * thread per edge, at the current poses: s_e = info[e] |e_e|^2 with the same
+ * residual e_e as the iteration's linearisation, the ratio r_e = rho'(s_e) of
+ * the loss (1 where robust_mask[e] == 0), and
+ *   w_out[e] = info[e] r_e          the array the next iteration reads as w
+ *   s_out[e] = s_e, ratio_out[e] = r_e
+ *   cost_partials[g], smax_partials[g]   per workgroup g of
+ *       SLAM_GN_ROBUST_BLOCK edges ((E + 255) / 256 of each): the sum of
+ *       rho(s_e) over the masked edges plus s_e over the others, in a fixed
+ *       order, and the largest masked s_e (0 without one).
+ * loss: SLAM_LOSS_*; c > 0 is the loss scale in units of sqrt(info) x
+ * residual, c2 = c^2; mu >= 1 scales c2 for SLAM_LOSS_GNC_GM (graduated
+ * non-convexity, the caller lowers mu towards 1) and is ignored otherwise:
+ *   huber    r = 1 (s <= c2), else c / sqrt(s)
+ *   cauchy   r = 1 / (1 + s / c2)
+ *   gm       r = (c2 / (c2 + s))^2             (Geman-McClure)
+ *   dcs      r = min(1, 2 c2 / (c2 + s))^2     (dynamic covariance scaling)
+ * Arguments are checked before the launch (SLAM_EINVAL); E == 0 does nothing.
+ */
+#define SLAM_LOSS_HUBER 0
+#define SLAM_LOSS_CAUCHY 1
+#define SLAM_LOSS_GM 2
+#define SLAM_LOSS_DCS 3
+#define SLAM_LOSS_GNC_GM 4
+#define SLAM_GN_ROBUST_BLOCK 256
+int slam_gn_robust_weights_f64(const double* poses, const int32_t* ea,
+                               const int32_t* eb, const double* tf,
+                               const double* info, const uint8_t* robust_mask,
+                               int32_t E, int32_t loss, double c, double mu,
+                               double* w_out, double* s_out, double* ratio_out,
+                               double* cost_partials, double* smax_partials,
+                               void* stream);
+
 /* ---- occupancy grid (src/produce_occupancy_grid.py) ------------------------
  * pts: packed (x, y) scan points, scan_off (S+1), pose4 (S x 4: cos theta,
  * sin theta, x, y of each scan's pose; cos/sin as np.cos/np.sin give them).
