@@ -14,7 +14,9 @@ closures are rejected too.
 
 The reference has no counterpart.  include/slamhip.h states the rule,
 tests/pcm_ref.py restates it in NumPy and tests/test_pcm_gpu.py compares bit
-for bit.
+for bit; tests/pcm_cases.py holds hand-placed inputs for every peel slot, tile
+edge and the capacity, checked on the CPU by tests/test_pcm_cases.py and run on
+the GPU by tests/test_pcm_paths_gpu.py.
 """
 from dataclasses import dataclass
 
